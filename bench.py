@@ -3,8 +3,17 @@ Msamples/s at 1920x1080x1024spp (config C3: 6-sphere union/difference CSG +
 sky wall, depth 8), with the per-channel RMSE of the GPU frame against the
 reference CPU renderer on a hashed pixel subset.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line (the
+roofline figures in it come from the timed steps' own HIP events).  --full adds
+what takes a run of its own: the CPU baseline and the RMSE of the GPU frame
+against it.  --dump-outputs DIR writes the frame of the last timed step as
+DIR/frame.npy (H x W x 3 float32; a frame above the 64 MB cap is written as a
+fixed seeded pixel sample, frame.npy = npix x 3 and frame_pixels.npy = their
+indices y * W + x as float64).  The scene, the seed and the sample are fixed, so
+the same arguments give the same inputs from run to run.
 
 Launch.  Without torchrun (no WORLD_SIZE in the environment) and --gpus N > 1,
 this process starts N rank processes itself (a torch.distributed.run child on
@@ -26,7 +35,7 @@ resident before timing.
 
 Extra fields: `roofline` (VALU-bound: the SURVEY.md s8(d) FP32 op model per
 root query x the kernel's exact query count / HIP-event kernel time, against
-78.6 T non-FMA FP32 op/s) and `cpu_baseline` (the unmodified reference sources,
+78.6 T non-FMA FP32 op/s) and, with --full, `cpu_baseline` (the unmodified reference sources,
 oracle/_ref/ptref, on the GPU box's host cores over a bounded pixel sample of
 the same frame, rank 0 only).
 """
@@ -97,7 +106,12 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = the CPUs this process may run on (sched_getaffinity), capped by OMP_NUM_THREADS "
                          "when set (the GPU box exports its per-GPU CPU share there)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the RMSE against it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write the last timed step's frame as DIR/frame.npy (float32, at most 64 MB: a "
+                         "larger frame as a fixed seeded pixel sample with DIR/frame_pixels.npy)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline (a plain run has none)")
     ap.add_argument("--cpu-at-n", action="store_true",
                     help="N > 1: also run the CPU baseline and the RMSE on rank 0 (default: the N = 1 line only)")
     ap.add_argument("--dump-frame", default="", help="rank 0: save the reduced frame (H x W x 3 f32 .npy)")
@@ -117,7 +131,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch and rank plumbing only (process group, barrier, max over ranks, rank 0's line) "
                          "with no render: prints a line with value null and dry_run true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port() -> int:
@@ -280,6 +297,25 @@ def cpu_baseline(cfg, txt, spp, npix, threads, frame_qps, within=None):
     return pix, res, out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, frame: np.ndarray) -> None:
+    """--dump-outputs: the frame a caller of the timed path receives (H x W x 3
+    float32), whole when it fits the cap, else a fixed seeded sample of its
+    pixels with their indices beside it."""
+    os.makedirs(path, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_CAP_BYTES:
+        np.save(os.path.join(path, "frame.npy"), frame)
+        return
+    flat = frame.reshape(-1, 3)
+    npix = DUMP_CAP_BYTES // (3 * 4 + 8)  # a pixel's three floats and its float64 index
+    pix = np.sort(np.random.default_rng(0x5EED).choice(len(flat), npix, replace=False))
+    np.save(os.path.join(path, "frame.npy"), flat[pix])
+    np.save(os.path.join(path, "frame_pixels.npy"), pix.astype(np.float64))
+
+
 def main():
     args = parse()
     status = launch_check(args)
@@ -394,13 +430,18 @@ def main():
         npix_total = subset if subset else W * H
         samples = npix_total * spp * args.steps
         value = samples / elapsed / 1e6
-        frame = fb.view(H, W, 3).cpu().numpy()
+        cpu_leg = args.full and not args.no_cpu and (world == 1 or args.cpu_at_n)
+        frame = None
+        if args.dump_frame or args.dump_outputs or cpu_leg:
+            frame = fb.view(H, W, 3).cpu().numpy()
         if args.dump_frame:
             np.save(args.dump_frame, frame)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
         out = {
             "metric": "Msamples/sec at 1920x1080x1024spp; per-channel RMSE vs CPU ref",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 1), "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "kernel_key": kernel_key,
             "config": {"workload": "%s: %dx%d, %d spp, depth %d, %s%s" % (
@@ -452,7 +493,9 @@ def main():
                     "salu_insts_per_simd_cycle": round(ev.get("salu_insts_per_simd_cycle", 0), 4),
                     "valu_busy_rocprof": round(ev["valu_busy"], 4),
                     "hbm_GBps": round(ev["hbm_GBps"], 2), "hbm_peak_GBps": 8000.0})
-        if world > 1 and not args.no_cpu and not args.cpu_at_n:
+        if not args.full:  # a plain run: the timed steps only
+            pass
+        elif world > 1 and not args.no_cpu and not args.cpu_at_n:
             # the CPU baseline is the N = 1 line's (rank 0 at N = 1 only); an N-rank frame is the
             # one-GPU frame bit for bit (tiles) or within ~1e-7 (sample split), tests/test_bench_dist.py
             out["cpu_baseline"] = {"note": "reported on the N = 1 line (bench.py --gpus 1); --cpu-at-n adds it here"}

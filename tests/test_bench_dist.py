@@ -46,7 +46,7 @@ def test_bench_two_ranks_gloo(tmp_path, split):
     # block-staged path (whole 32-sample blocks) a real rank share takes
     common = ["--config", "C3", "--spp", "256", "--steps", "1", "--warmup", "0", "--cpu-pixels", "16"]
     one, f1 = _bench(common + ["--no-cpu"], 1, tmp_path, "one")
-    two, f2 = _bench(common + ["--backend", "gloo", "--split", split, "--cpu-at-n"], 2, tmp_path, "two")
+    two, f2 = _bench(common + ["--backend", "gloo", "--split", split, "--full", "--cpu-at-n"], 2, tmp_path, "two")
     assert two["n_gpus"] == 2 and two["steps"] == 1
     assert "gloo reduce" in two["config"]["sharding"]
     assert ("spp split" in two["config"]["sharding"]) == (split == "samples")
@@ -70,6 +70,28 @@ def test_bench_two_ranks_gloo(tmp_path, split):
     else:  # the ranks' partial sums change the association only
         rmse = np.sqrt(np.mean((f2.astype(np.float64) - f1) ** 2, axis=(0, 1)))
         assert rmse.max() <= 1e-6, rmse
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_frame(tmp_path):
+    """A plain run times its steps only (no CPU leg in its line) and
+    --dump-outputs writes the frame of the last timed step; --full adds the
+    CPU baseline and the RMSE against it on the same frame."""
+    common = ["--config", "C3", "--spp", "32", "--steps", "2", "--warmup", "1", "--cpu-pixels", "16"]
+    out = str(tmp_path / "outputs")
+    plain, f1 = _bench(common + ["--dump-outputs", out], 1, tmp_path, "plain")
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    assert plain["value"] == pytest.approx(plain["samples_per_step"] / plain["ms_per_step"] / 1e3, rel=1e-3)
+    assert "cpu_baseline" not in plain and "rmse_vs_cpu_ref" not in plain
+    assert plain["roofline"]["avg_launch_ms"] > 0
+    assert os.listdir(out) == ["frame.npy"]
+    dumped = np.load(os.path.join(out, "frame.npy"))
+    assert dumped.dtype == np.float32 and dumped.shape == (1080, 1920, 3)
+    np.testing.assert_array_equal(dumped.view(np.uint32), f1.view(np.uint32))
+    full, f2 = _bench(common + ["--full"], 1, tmp_path, "full")
+    assert full["cpu_baseline"]["kind"] in ("reference", "port") and full["cpu_baseline"]["value"] > 0
+    assert max(full["rmse_vs_cpu_ref"]) < 1e-3
+    np.testing.assert_array_equal(f2.view(np.uint32), f1.view(np.uint32))
 
 
 @pytest.mark.gpu

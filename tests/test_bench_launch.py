@@ -70,6 +70,36 @@ def test_more_gpus_than_visible_exits_nonzero():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_dump_outputs_whole_frame_and_capped_sample(tmp_path):
+    """--dump-outputs: a frame within the 64 MB cap is written whole as float32;
+    a larger one as the same seeded pixel sample on every call, indices beside it"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.random((27, 41, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert os.listdir(tmp_path / "a") == ["frame.npy"]
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    H, W = 2160, 3840  # C5's whole frame: 99.5 MB
+    big = np.arange(H * W * 3, dtype=np.float32).reshape(H, W, 3)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    f, p = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "b" / "frame_pixels.npy")
+    assert f.dtype == np.float32 and p.dtype == np.float64
+    assert f.nbytes + p.nbytes <= 64 << 20 and len(f) == len(p) > (H * W) // 3
+    idx = p.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < H * W
+    assert np.array_equal(f, big.reshape(-1, 3)[idx])
+    assert np.array_equal(p, np.load(tmp_path / "c" / "frame_pixels.npy"))
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-run"], timeout=60)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_split_env_parsed_like_the_runtime():
     """PT_SPLIT is read with the runtime's atoi rule (runtime.cpp split_launches)"""
     sys.path.insert(0, ROOT)

@@ -10,8 +10,8 @@ The synthetic files come from a small encoder in this test (every filter type,
 both interlace modes); the expected images are computed from the source pixels
 with the rules above, independently of any decoder, and PIL (present here)
 cross-checks that the files are valid PNGs.  The reference's own PNG assets
-(test.png, image.png, sky01/) are compared against PIL's decode when
-/root/reference is mounted.  libpng itself is not available here, so parity
+(test.png and image.png in tests/golden/, sky01/ in assets/) are compared
+against PIL's decode.  libpng itself is not available here, so parity
 with it rests on these rules: "parity unpinned" against libpng's binary.
 """
 import os
@@ -221,11 +221,15 @@ def test_reference_test_png_fixture(built):
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sky01"), reason="reference assets not mounted")
+ASSETS = os.path.join(os.path.dirname(os.path.dirname(__file__)), "assets")
+
+
 @pytest.mark.parametrize("name", ["image.png", "sky01/top.png", "sky01/front.png"])
 def test_reference_assets_match_pil(built, name):
+    """The reference's own PNG assets, kept in the tree: image.png as a fixture
+    in tests/golden/, the sky box faces in assets/sky01/."""
     from PIL import Image as PILImage
-    path = os.path.join("/root/reference", name)
+    path = os.path.join(GOLD, name) if name == "image.png" else os.path.join(ASSETS, name)
     raw = PILImage.open(path)
     e = np.asarray(raw.convert("RGBA")).astype(np.int64)
     if raw.mode == "RGB":

@@ -5,7 +5,8 @@
 # STEPs
 #   tests                 pytest -m gpu (whole suite)            tests:EXPR  only -k EXPR
 #   smoke                 __graft_entry__.smoke()
-#   bench:CFG[:ARGS]      bench.py --config CFG, ARGS comma-separated (e.g. bench:C3:--steps,2)
+#   bench:CFG[:ARGS]      bench.py --full --config CFG (with the CPU baseline), ARGS comma-separated
+#                         (e.g. bench:C3:--steps,2)
 #   dist:CFG              bench.py --force-dist: the N > 1 step (RCCL group, per-pixel sums,
 #                         device reduce) at world size 1, frame dumped beside the plain one
 #   ab:SPP:REPS:H1,H2     interleaved same-box A/B of device-library headers on the C3
@@ -46,7 +47,7 @@ for step in "$@"; do
   bench)
     IFS=, read -r -a EXTRA <<< "$b"
     tag=$a; [ -n "$b" ] && tag="${a}_$(echo "$b" | tr -c 'A-Za-z0-9' '_')"
-    run 900 "$OUT/bench_$tag.log" python3 bench.py --config "$a" "${EXTRA[@]}"
+    run 900 "$OUT/bench_$tag.log" python3 bench.py --full --config "$a" "${EXTRA[@]}"
     grep '^{' "$OUT/bench_$tag.log" > "$OUT/bench_$tag.json"; cut -c1-400 "$OUT/bench_$tag.json" ;;
   dist)
     run 900 "$OUT/plain_$a.log" python3 bench.py --config "$a" --no-cpu --dump-frame "$OUT/plain_$a.npy"
