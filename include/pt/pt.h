@@ -356,6 +356,13 @@ int pt_scene_set_split(pt_scene *s, int on);
  * the compiler options and the hiprtc version -- the file name of its entry in
  * the code-object cache (hex string, thread-local storage). */
 const char *pt_scene_kernel_key(pt_scene *s, int depth);
+/* What code generation proved about the scatter bursts this scene's materials
+ * can reach; the render kernel is compiled with only those variants.
+ * *kr_reach: bit 0 = a burst with scatter coefficient exactly 1 is possible,
+ * bit 1 = one with another coefficient (3 = both or unknown, 0 = no material
+ * scatters).  *bursts_all_leaf: 1 when every child of every burst is provably
+ * a leaf (strength below eps), else 0.  Either pointer may be null. */
+int pt_scene_reach_facts(pt_scene *s, int *kr_reach, int *bursts_all_leaf);
 
 /* ------------------------------------------------------------ queries --- */
 /* The reference's query virtuals, evaluated on the device.

@@ -92,6 +92,66 @@ struct Gen
         return INF;
     }
 
+    /* A bound on length(getColor) of texture id: the constant's own length for
+     * a ColorTexture, sqrt(3) x the channel bound otherwise. */
+    double length_bound(int id) const
+    {
+        const TexRec &x = s.textures.at(id);
+        if (x.kind == TexKind::Color) {
+            double q = 0.0;
+            for (int c = 0; c < 3; c++) {
+                if (!(std::fabs(x.f[c]) <= FLT_MAX))
+                    return HUGE_VAL;
+                q += (double)x.f[c] * (double)x.f[c];
+            }
+            return std::sqrt(q);
+        }
+        return std::sqrt(3.0) * color_bound(id);
+    }
+
+    /* Which scatter bursts the scene's materials can reach (pt_device.h burst(),
+     * PT_REACH_PRUNE), from the materials of the tree alone.
+     *
+     * A material enters a burst only when sc = clamp01(getFloat(scatter)) > EPS
+     * (PH_LOOP).  sc is known when the scatter texture is a ColorTexture: the
+     * device computes clamp01(mean3(constant)), restated here in float.  kr:
+     * bit 0 = a burst with sc == 1.0f is possible (burst_t KR0), bit 1 = one
+     * with sc != 1.0f; any other scatter texture sets both.
+     *
+     * all_leaf: burst()'s `deferred` holds for every burst.  A burst has
+     *   x = fl(fl(fl(10000 str) add) sc),  N = (int)x if x >= 1, else 1
+     * (N = INT_MIN from an out-of-range x never loops: i >= N at once), and
+     *   sNa = fl(fl(str / (float)N) add),  tested as fl(fl(sNa |rc|) 1.01f) < EPS.
+     * x < N + 1 <= 2 N when x >= 1 and x / N < 1 otherwise, so in real numbers
+     * str add / N < 2e-4 / sc, and the test's left side is below
+     *   (2e-4 / sc) |rc| 1.01 (1 + d)^k,   d = 2^-24,
+     * with k <= 12 roundings: three in x, (float)N, two in sNa, two in the
+     * test and four in length(rc).  (1 + d)^12 < 1 + 1e-6; the margin below is
+     * 1e-5, and 1.01f < 1.01, EPS = 1e-3f > 1e-3 both help.  No step comes near
+     * the subnormals: str / N >= 1 / (2e4 add sc) when x >= 1, str >= EPS else.
+     * |rc| <= length_bound of the reflect texture.  A material with an unknown
+     * sc or an unbounded reflect makes the fact false: nothing is pruned. */
+    void reach_facts(int &kr, bool &all_leaf) const
+    {
+        kr = 0, all_leaf = true;
+        for (int id : mats) {
+            const MatRec &m = s.materials.at(id);
+            const TexRec &x = s.textures.at(m.scatter);
+            if (x.kind != TexKind::Color) {
+                kr = 3, all_leaf = false;
+                continue;
+            }
+            const float mean = ((x.f[0] + x.f[1]) + x.f[2]) * (1.0f / 3.0f); /* pt_device.h mean3 */
+            const float lo = (mean < 1.0f) ? mean : 1.0f;                    /* pt_device.h clamp01 */
+            const float sc = (0.0f < lo) ? lo : 0.0f;
+            if (!(sc > 1e-3f)) /* EPS: a mirror child, no burst */
+                continue;
+            kr |= sc == 1.0f ? 1 : 2;
+            if (!((2e-4 / (double)sc) * length_bound(m.reflect) * 1.01 * (1.0 + 1e-5) < 1e-3))
+                all_leaf = false;
+        }
+    }
+
     int put(const float *v, int n)
     {
         int off = (int)P.size();
@@ -473,6 +533,13 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     for (size_t k = 0; k < g.mats.size() && emis_finite; k++)
         emis_finite = g.color_bound(s.materials.at(g.mats[k]).emissive) <= (double)FLT_MAX;
     src << "  static constexpr bool emis_finite = " << (emis_finite ? "true" : "false") << ";\n";
+    /* kr_reach, bursts_all_leaf: the burst variants the materials can reach
+     * (Gen::reach_facts; pt_device.h PT_REACH_PRUNE instantiates only those) */
+    int kr_reach = 0;
+    bool bursts_all_leaf = false;
+    g.reach_facts(kr_reach, bursts_all_leaf);
+    src << "  static constexpr int kr_reach = " << kr_reach << ";\n";
+    src << "  static constexpr bool bursts_all_leaf = " << (bursts_all_leaf ? "true" : "false") << ";\n";
     if (all_emis_const && lit_mats.size() <= 4) {
         /* few constant emitters: a select chain on scalar-loaded constants
          * (dark materials keep the exact (+0, +0, +0)) instead of a per-lane
@@ -512,6 +579,8 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     out.n_planes = g.planes;
     out.n_mats = (int)g.mats.size();
     out.mat_ids = g.mats;
+    out.kr_reach = kr_reach;
+    out.bursts_all_leaf = bursts_all_leaf;
     char key[40];
     snprintf(key, sizeof key, "%016llx", (unsigned long long)fnv1a(out.source));
     out.key = key;

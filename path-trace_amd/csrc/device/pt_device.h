@@ -3732,24 +3732,51 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
  * possible factor (1 + 4e-7: wn and n are unit vectors) keeps the child
  * strength below eps.  Then acceptance needs no normalisation, and the
  * normalised direction / factor are computed per child at trace time (same
- * arithmetic, same bits) with every lane busy. */
+ * arithmetic, same bits) with every lane busy.
+ *
+ * burst_t is the largest function of the kernel, and a scene's materials
+ * usually reach one of its three variants.  Code generation decides which
+ * (codegen.cpp reach_facts: Scene::kr_reach, bit 0 = a burst with sc == 1 is
+ * possible, bit 1 = one with sc != 1; Scene::bursts_all_leaf = the strength
+ * test below holds for every burst, proven from the materials' constants),
+ * and PT_REACH_PRUNE instantiates only the reachable ones: the tests that
+ * remain pick among variants that are all reachable, so the bits are the
+ * same.  PT_REACH_PRUNE=0 keeps the three-way runtime dispatch. */
+#ifndef PT_REACH_PRUNE
+#define PT_REACH_PRUNE 1
+#endif
+template <class S>
+struct Reach
+{
+    static constexpr int kr = PT_REACH_PRUNE ? S::kr_reach : 3;
+    static constexpr bool all_leaf = PT_REACH_PRUNE ? S::bursts_all_leaf : false;
+};
 template <class S, bool STRICT>
 __device__ __forceinline__ int burst(const Env &e, Rng &rng, const u64 *__restrict__ jump, const JumpLds &jl,
                                      const WaveLds &L, Frame &f, Frame &child, Counters &cnt)
 {
-    const float sNa = unif((unif(f.strength) / (float)uni(f.N)) * unif(f.add));
-    const float abs_rc = unif(length(univ(f.rc)));
-    const bool deferred = uni(f.depth) - 1 <= 0 || (sNa * abs_rc * 1.01f < EPS);
+    [[maybe_unused]] bool deferred = true;
+    if constexpr (!Reach<S>::all_leaf) {
+        const float sNa = unif((unif(f.strength) / (float)uni(f.N)) * unif(f.add));
+        const float abs_rc = unif(length(univ(f.rc)));
+        deferred = uni(f.depth) - 1 <= 0 || (sNa * abs_rc * 1.01f < EPS);
+    }
     PT_T0(t0);
     int r;
-    if (deferred) {
-        if (unif(f.sc) == 1.0f)
-            r = burst_t<S, STRICT, true, true>(e, rng, jump, jl, L, f, child, cnt);
-        else
-            r = burst_t<S, STRICT, true, false>(e, rng, jump, jl, L, f, child, cnt);
-    } else {
-        r = burst_t<S, STRICT, false, false>(e, rng, jump, jl, L, f, child, cnt);
-    }
+    if constexpr (!Reach<S>::all_leaf)
+        if (!deferred) {
+            r = burst_t<S, STRICT, false, false>(e, rng, jump, jl, L, f, child, cnt);
+            PT_ACC(cnt, 5, t0);
+            return r;
+        }
+    if constexpr (Reach<S>::kr == 1)
+        r = burst_t<S, STRICT, true, true>(e, rng, jump, jl, L, f, child, cnt);
+    else if constexpr (Reach<S>::kr == 2)
+        r = burst_t<S, STRICT, true, false>(e, rng, jump, jl, L, f, child, cnt);
+    else if (unif(f.sc) == 1.0f)
+        r = burst_t<S, STRICT, true, true>(e, rng, jump, jl, L, f, child, cnt);
+    else
+        r = burst_t<S, STRICT, true, false>(e, rng, jump, jl, L, f, child, cnt);
     PT_ACC(cnt, 5, t0);
     return r;
 }
@@ -4236,6 +4263,8 @@ __device__ __forceinline__ bool lane_walk_sc(const Env &e, int depth0, V3 o0, V3
                 /* a loop likely to form a run of more than 64 terms: every
                  * child is a leaf, or few recurse (factor >= eps / (sNa |rc|)
                  * with factor = 1 - (1 - cos) sc) */
+                if constexpr (Reach<S>::all_leaf) /* burst()'s test, proven for this scene */
+                    return false;
                 const float sNa = (c.str / (float)N) * c.add, abs_rc = length(rc);
                 const bool all_leaf = c.dep - 1 <= 0 || sNa * abs_rc * 1.01f < EPS;
                 if (all_leaf || (1.0f - EPS / (sNa * abs_rc)) < 0.15f * sc)
@@ -4454,7 +4483,8 @@ __device__ __forceinline__ V3 trace_sample(const Env &e, const PtLaunch &lp, int
                 phase = PH_RETURN;
                 continue;
             }
-            if (unif(f.sc) > EPS) {
+            /* kr == 0: no material of the scene has sc > EPS, no burst exists */
+            if (Reach<S>::kr != 0 && unif(f.sc) > EPS) {
                 int why = burst<S, STRICT>(e, rng, jump, jl, L, f, F[sp + 1], cnt);
                 if (why != B_NONLEAF) {
                     result = univ(f.retval);

@@ -106,6 +106,8 @@ struct Generated
     int maxd = 0;
     int n_prims = 0, n_spheres = 0, n_planes = 0, n_mats = 0;
     std::vector<std::string> options; /* per-scene compiler options (part of the code-object key) */
+    int kr_reach = 3;                 /* burst variants reachable: bit 0 sc == 1, bit 1 sc != 1 (codegen reach_facts) */
+    bool bursts_all_leaf = false;     /* every burst's children are provably leaves */
 };
 
 /* rays: the module of pt_trace_rays (PT_RAYS), whose items are caller rays */

@@ -1546,6 +1546,18 @@ const char *pt_scene_kernel_key(pt_scene *s, int depth)
     return k.c_str();
 }
 
+int pt_scene_reach_facts(pt_scene *s, int *kr_reach, int *bursts_all_leaf)
+{
+    return guard([&] {
+        const Generated g = generate(S(s), 1); /* the facts depend on the materials only */
+        if (kr_reach)
+            *kr_reach = g.kr_reach;
+        if (bursts_all_leaf)
+            *bursts_all_leaf = g.bursts_all_leaf ? 1 : 0;
+        return PT_OK;
+    });
+}
+
 int pt_prepare(pt_scene *s, const pt_render_params *p)
 {
     return guard([&] {

@@ -191,6 +191,16 @@ class DeviceScene:
             raise PtError(_lib.lib().pt_last_error().decode())
         return k
 
+    @property
+    def reach_facts(self) -> dict:
+        """What code generation proved about this scene's scatter bursts
+        (pt_scene_reach_facts): {"kr_reach": 0..3 (bit 0: a burst with scatter
+        coefficient 1 is possible, bit 1: one with another coefficient),
+        "bursts_all_leaf": every burst child is provably a leaf}."""
+        kr, leaf = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.lib().pt_scene_reach_facts(self._h, ctypes.byref(kr), ctypes.byref(leaf)))
+        return {"kr_reach": kr.value, "bursts_all_leaf": bool(leaf.value)}
+
     def compile_rays(self, depth: int) -> None:
         """Compile pt_trace_rays' module for this scene and depth (no device)."""
         _lib.check(_lib.lib().pt_trace_compile(self._h, depth))

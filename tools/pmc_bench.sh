@@ -5,6 +5,7 @@
 #   busy   issue/busy counters        fetch  FETCH_SIZE     write  WRITE_SIZE
 #   stall  wave-cycle split + memory instruction mix     cache  L2 hits/misses
 #   tex    texture address/data unit busy (TA, TD) and flat read wavefronts
+#   ifetch instruction fetches of the waves and the instruction cache's requests, hits, misses
 # usage: tools/pmc_bench.sh OUTDIR [bench args...]
 OUT=${1:-gpurun_out/pmcb}; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -23,4 +24,6 @@ pass write WRITE_SIZE
 pass stall SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_FLAT SQ_INSTS_LDS SQ_INSTS_SMEM
 pass cache TCC_HIT_sum TCC_MISS_sum
 pass tex TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum TD_TD_BUSY_sum GRBM_GUI_ACTIVE
+# optional: the summary goes without it where these counters cannot be collected
+(pass ifetch SQ_IFETCH SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE) || rm -rf "$OUT/ifetch"
 python3 "$ROOT/tools/pmc_summary.py" "$OUT" > "$OUT/pmc.json" && cat "$OUT/pmc.json"

@@ -9,12 +9,20 @@ summed over waves) x 4 / SIMDs / GRBM_GUI_ACTIVE per XCD (GRBM is summed over
 the 8 XCDs).  It counts one quad-cycle per VALU instruction, so it measures
 VALU issue occupancy, not lane utilisation.  HBM bytes: FETCH_SIZE doubled
 (gfx950 tallies 128-B requests at 64 B, MI355X_MICROARCH.md) + WRITE_SIZE,
-both in KB.  usage: pmc_summary.py OUTDIR"""
+both in KB.  The instruction-fetch pass (ifetch) is optional: its counters are
+summed over the SQCs, one per pair of CUs.  The code object's static figures
+(spill counts, private segment, pt_render_fast's code bytes) are read from the
+code-object cache entry the key names.  usage: pmc_summary.py OUTDIR"""
 import collections
 import csv
 import glob
 import json
+import os
 import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools", "ab"))
+import isa_stat  # noqa: E402
 
 out = sys.argv[1]
 SIMDS, XCDS = 1024, 8
@@ -44,9 +52,11 @@ def bench_line(name):
 
 busy, fetch, write = counters("busy"), counters("fetch"), counters("write")
 stall, cache, tex = counters("stall"), counters("cache"), counters("tex")
+ifetch = counters("ifetch")
 b = bench_line("busy")
 # the code object every pass ran (bench.py attaches this file only to a line that timed the same one)
-keys = {bench_line(n).get("kernel_key") for n in ("busy", "fetch", "write", "stall", "cache", "tex")}
+keys = {bench_line(n).get("kernel_key") for n in ("busy", "fetch", "write", "stall", "cache", "tex") +
+        (("ifetch",) if ifetch else ())}
 if len(keys) != 1 or None in keys:
     raise SystemExit("passes ran different or unknown code objects: %s" % sorted(map(str, keys)))
 launches = b["steps"]  # one render launch per step at the bench config (one pass)
@@ -77,6 +87,21 @@ if stall:
                                "issuing": stall["SQ_ACTIVE_INST_ANY"] / wc}
     for k in ("SQ_INSTS_VMEM_RD", "SQ_INSTS_FLAT", "SQ_INSTS_LDS", "SQ_INSTS_SMEM"):
         res[k.lower()[9:] + "_insts_per_sample"] = stall[k] / samples
+hsaco = os.path.join(ROOT, "path-trace_amd", "_jit_cache", b["kernel_key"] + ".hsaco")
+if os.path.exists(hsaco):
+    meta = isa_stat.metadata(hsaco)
+    res["code_object"] = {"sgpr_spill_count": meta.get("sgpr_spill_count"),
+                          "vgpr_spill_count": meta.get("vgpr_spill_count"),
+                          "private_segment_fixed_size": meta.get("private_segment_fixed_size"),
+                          "pt_render_fast_code_bytes": meta.get("code_bytes")}
+if ifetch:
+    req = ifetch["SQC_ICACHE_REQ"]
+    res["icache"] = {"hit_rate": ifetch["SQC_ICACHE_HITS"] / max(1.0, req),
+                     "miss_rate": (ifetch["SQC_ICACHE_MISSES"] + ifetch["SQC_ICACHE_MISSES_DUPLICATE"]) / max(1.0, req),
+                     "requests_per_sample": req / samples,
+                     "misses_per_sample": ifetch["SQC_ICACHE_MISSES"] / samples,
+                     "duplicate_misses_per_sample": ifetch["SQC_ICACHE_MISSES_DUPLICATE"] / samples,
+                     "wave_ifetches_per_sample": ifetch["SQ_IFETCH"] / samples}
 if cache:
     res["l2_hit_rate"] = cache["TCC_HIT_sum"] / max(1.0, cache["TCC_HIT_sum"] + cache["TCC_MISS_sum"])
 if tex:
