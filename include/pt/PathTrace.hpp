@@ -690,9 +690,11 @@ public:
      * next() walks the returned list (bit-identical to the reference's lazy
      * iterators, Difference quirk included).  A user-defined subclass
      * overrides it as in the reference (host-side), and gets a device form --
-     * renders, device span queries -- when its iterator yields one span per
-     * ray and it returns that span's arithmetic as device source
-     * (deviceSpan / deviceNormal below, pt_object_device). */
+     * renders, device span queries -- when it returns its iterator's
+     * arithmetic as device source: one span per ray through deviceSpan /
+     * deviceNormal (pt_object_device), or a bounded list of ordered, strictly
+     * separated spans -- a shell, a torus, user-side CSG -- through
+     * deviceSpans / deviceMaxSpans / deviceNormal (pt_object_device_spans). */
     inline virtual SpanIterator *makeSpanIterator() const;
     virtual Object *transform(const Matrix &) const { return nullptr; }
     virtual Object *duplicate() const = 0;
@@ -701,6 +703,12 @@ public:
      * its parameters `const float *prm` (deviceParams), and its material. */
     virtual const char *deviceSpan() const { return nullptr; }
     virtual const char *deviceNormal() const { return nullptr; }
+    /* The span-list form: the body of int spans(V3 o, V3 d, float *t0, float *t1)
+     * (the number of spans, at most deviceMaxSpans() <= PT_OBJECT_MAX_SPANS,
+     * t0[k] <= t1[k] < t0[k + 1]); deviceNormal() is then the body of
+     * V3 normal(V3 p, int k), the outward normal at boundary point p of span k. */
+    virtual const char *deviceSpans() const { return nullptr; }
+    virtual int deviceMaxSpans() const { return 1; }
     virtual std::vector<float> deviceParams() const { return std::vector<float>(); }
     virtual const Material *deviceMaterial() const { return nullptr; }
     inline virtual pt_id flatten(Flattener &f) const;
@@ -708,11 +716,14 @@ public:
 
 inline pt_id Object::flatten(Flattener &f) const
 {
-    const char *sp = deviceSpan(), *nb = deviceNormal();
-    if (!sp || !nb || !deviceMaterial())
+    const char *sp = deviceSpan(), *nb = deviceNormal(), *sl = deviceSpans();
+    if ((!sp && !sl) || !nb || !deviceMaterial())
         throw DeviceError(PT_ERR_ARG, "a user-defined Object subclass has no device form "
-                                      "(override deviceSpan, deviceNormal and deviceMaterial)");
+                                      "(override deviceSpan or deviceSpans, deviceNormal and deviceMaterial)");
     const std::vector<float> prm = deviceParams();
+    if (sl)
+        return ptCheck(pt_object_device_spans(f.s, sl, nb, prm.data(), (int)prm.size(), deviceMaxSpans(),
+                                              f.material(deviceMaterial())));
     return ptCheck(pt_object_device(f.s, sp, nb, prm.data(), (int)prm.size(), f.material(deviceMaterial())));
 }
 

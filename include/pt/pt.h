@@ -130,6 +130,32 @@ pt_id pt_transformed(pt_scene *s, const float m[12], pt_id child);             /
  * primitive; the kernel's fast paths treat it conservatively (never dark). */
 pt_id pt_object_device(pt_scene *s, const char *span_body, const char *normal_body, const float *params,
                        int nparams, pt_id mat);
+/* The same for a subclass whose iterator yields several spans per ray
+ * (include/object.h:14-20: makeSpanIterator returns any SpanIterator;
+ * include/span.h:129-171: init(ray), then next() until isAtEnd()) -- a hollow
+ * shell, a torus, a dumbbell, user-side CSG -- as a bounded span list
+ * (path-trace_amd/csrc/device/pt_user_object_n.h).  spans_body is the body of
+ *     int spans(V3 o, V3 d, float *t0, float *t1)
+ * returning the number n of spans, 0 <= n <= max_spans, the ray o + t d (d not
+ * normalised) has with the object, and filling t0[k] <= t1[k] for k < n in ray
+ * order and strictly separated: t1[k] < t0[k + 1]; normal_body is the body of
+ *     V3 normal(V3 p, int k)
+ * returning the outward surface normal at the boundary point p of span k (its
+ * start normal at the entry point, its end normal at the exit; traceRay flips
+ * the end normal itself).  Parameters (`const float *prm`), vocabulary and
+ * arithmetic are pt_object_device's: no FMA contraction, correctly rounded '/'
+ * and sqrt.  max_spans is 1..PT_OBJECT_MAX_SPANS (1 is legal: one span, with
+ * these signatures); each span takes one primitive slot of the tree, i.e.
+ * three words of registers per lane in the kernel's fast checks, so declare
+ * what the shape needs (a shell 2, a torus 4) -- 8 is a design bound, not a
+ * measured one.  A body that breaks its contract (a count above max_spans,
+ * unordered or touching spans) gives wrong pixels, never an access out of
+ * range.  All spans carry the one material.  PT_ERR_ARG, with the entry
+ * point's name in pt_last_error(): an empty body, a bad parameter block,
+ * max_spans out of range, a bad material. */
+#define PT_OBJECT_MAX_SPANS 8
+pt_id pt_object_device_spans(pt_scene *s, const char *spans_body, const char *normal_body, const float *params,
+                             int nparams, int max_spans, pt_id mat);
 int pt_set_root(pt_scene *s, pt_id obj);
 /* Load a whole scene from the plain-text scene format (oracle/scene_text.h
  * documents it; pathtrace.scene.to_text writes it).  Replaces the current

@@ -40,6 +40,7 @@ struct Gen
     std::vector<std::pair<size_t, int>> unit_planes; /* (position of the ",U" mark in a node string, axis) */
     std::map<int, int> user_tex; /* User texture id -> offset of its parameters in P */
     std::vector<int> user_obj;   /* User objects reached (their bodies become UObjB_<id>) */
+    bool multi_span = false;     /* one of them yields a span list (UObjN) */
 
     explicit Gen(const SceneImpl &sc) : s(sc) {}
 
@@ -236,6 +237,14 @@ struct Gen
             P.insert(P.end(), o.params.begin(), o.params.end());
             if (std::find(user_obj.begin(), user_obj.end(), id) == user_obj.end())
                 user_obj.push_back(id);
+            if (o.max_spans > 0) {
+                /* pt_object_device_spans: K consecutive primitive slots, one per span (device/pt_user_object_n.h) */
+                t << "UObjN<" << prim << "," << o.max_spans << "," << off << "," << material(o.mat) << ",UObjB_" << id
+                  << ">";
+                prim += o.max_spans;
+                multi_span = true;
+                break;
+            }
             t << "UObj<" << prim++ << "," << off << "," << material(o.mat) << ",UObjB_" << id << ">";
             break;
         }
@@ -342,6 +351,18 @@ struct Gen
         std::ostringstream d;
         for (int id : user_obj) {
             const ObjRec &o = s.objects.at(id);
+            if (o.max_spans > 0) {
+                d << "struct UObjB_" << id << " {\n"
+                  << "  __device__ static __forceinline__ int spans(V3 o, V3 d, const float *prm, float *t0, float *t1) {\n"
+                  << "    (void)prm;\n"
+                  << "#line 1 \"pt_object_device_spans " << id << " spans\"\n"
+                  << o.span_body << "\n  }\n"
+                  << "  __device__ static __forceinline__ V3 normal(V3 p, int k, const float *prm) {\n"
+                  << "    (void)prm, (void)k;\n"
+                  << "#line 1 \"pt_object_device_spans " << id << " normal\"\n"
+                  << o.normal_body << "\n  }\n};\n";
+                continue;
+            }
             d << "struct UObjB_" << id << " {\n"
               << "  __device__ static __forceinline__ bool span(V3 o, V3 d, const float *prm, float &t0, float &t1) {\n"
               << "    (void)prm;\n"
@@ -499,6 +520,8 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     }
     if (!g.user_obj.empty())
         src << device_user_object_source() << "\n";
+    if (g.multi_span)
+        src << device_user_object_n_source() << "\n";
     src << "namespace ptgen {\nusing namespace ptd;\n";
     src << g.user_defs();
     src << "typedef " << root << " RootT;\n";
@@ -599,6 +622,8 @@ Generated generate_query(const SceneImpl &s, int obj, int tex)
     src << device_library_source() << "\n";
     if (!g.user_obj.empty())
         src << device_user_object_source() << "\n";
+    if (g.multi_span)
+        src << device_user_object_n_source() << "\n";
     src << "namespace ptgen {\nusing namespace ptd;\n";
     src << g.user_defs();
     if (obj >= 0)

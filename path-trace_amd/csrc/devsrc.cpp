@@ -19,4 +19,11 @@ std::string device_user_object_source()
         ;
     return src;
 }
+std::string device_user_object_n_source()
+{
+    static const char src[] =
+#include "pt_user_object_n_src.inc"
+        ;
+    return src;
+}
 } // namespace pt

@@ -61,6 +61,9 @@ struct ObjRec
     /* User (pt_object_device): the caller's device bodies and parameters */
     std::string span_body, normal_body;
     std::vector<float> params;
+    /* User through pt_object_device_spans: the primitive slots its span list
+     * takes, 1..PT_OBJECT_MAX_SPANS (0 = pt_object_device's one-span form) */
+    int max_spans = 0;
 };
 
 struct DeviceState; /* runtime.cpp */
@@ -135,6 +138,7 @@ void write_bmp(const std::string &path, const float *rgb, int w, int h, int coun
 
 std::string device_library_source(); /* embedded pt_device.h */
 std::string device_user_object_source(); /* embedded pt_user_object.h (scenes with user objects) */
+std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scenes with multi-span user objects) */
 
 } // namespace pt
 

@@ -731,6 +731,7 @@ std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays)
         f.add(o.kind), f.add(o.mat), f.add(o.a), f.add(o.b);
         f.bytes(o.f, sizeof o.f);
         f.str(o.span_body.c_str()), f.str(o.normal_body.c_str());
+        f.add(o.max_spans);
         f.add(o.params.size());
         if (!o.params.empty())
             f.bytes(o.params.data(), o.params.size() * sizeof(float));
@@ -1447,6 +1448,35 @@ pt_id pt_object_device(pt_scene *s, const char *span_body, const char *normal_bo
         o.span_body = span_body;
         o.normal_body = normal_body;
         o.params.assign(params, params + nparams);
+        sc.objects.push_back(o);
+        return (int)sc.objects.size() - 1;
+    });
+}
+
+/* The same with a span list: up to max_spans ordered, strictly separated spans
+ * per ray (include/object.h:14-20, include/span.h:129-171), one primitive slot
+ * each (device/pt_user_object_n.h). */
+pt_id pt_object_device_spans(pt_scene *s, const char *spans_body, const char *normal_body, const float *params,
+                             int nparams, int max_spans, pt_id mat)
+{
+    return guard([&] {
+        SceneImpl &sc = S(s);
+        if (!spans_body || !*spans_body || !normal_body || !*normal_body)
+            throw Error(PT_ERR_ARG, "pt_object_device_spans: empty spans or normal body");
+        if (nparams < 0 || nparams > (1 << 16) || (nparams > 0 && !params))
+            throw Error(PT_ERR_ARG, "pt_object_device_spans: bad parameter block");
+        if (max_spans < 1 || max_spans > PT_OBJECT_MAX_SPANS)
+            throw Error(PT_ERR_ARG, "pt_object_device_spans: max_spans outside 1.." +
+                                        std::to_string(PT_OBJECT_MAX_SPANS));
+        if (mat < 0 || mat >= (pt_id)sc.materials.size())
+            throw Error(PT_ERR_ARG, "pt_object_device_spans: bad material id");
+        ObjRec o;
+        o.kind = ObjKind::User;
+        o.mat = mat;
+        o.span_body = spans_body;
+        o.normal_body = normal_body;
+        o.params.assign(params, params + nparams);
+        o.max_spans = max_spans;
         sc.objects.push_back(o);
         return (int)sc.objects.size() - 1;
     });

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import PT_ORDER_FAST, PT_ORDER_REFERENCE, PtError, RenderParams, RenderStats, TraceParams, load_hdr, \
     load_png, write_bmp, write_hdr
-from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceTexture, Difference, Image, ImageAlphaTexture, ImageSkyboxAlphaTexture,
+from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject, DeviceTexture, Difference, Image, ImageAlphaTexture, ImageSkyboxAlphaTexture,
                     ImageSkyboxTexture, ImageTexture, Intersection, LogTexture, Material, Matrix,
                     MirrorBallSkymapTexture, MultiplyTexture, Object, Plane, SphericalCoordinatesSkymapTexture,
                     Sphere, Texture, TransformedObject, TransformedTexture, Union, invert, to_text,
@@ -140,6 +140,10 @@ class DeviceScene:
             prm = (ctypes.c_float * max(1, len(o.params)))(*o.params)
             return c(L.pt_object_device(h, o.span_body.encode(), o.normal_body.encode(), prm, len(o.params),
                                         self._material(o.material)))
+        if isinstance(o, DeviceSpansObject):
+            prm = (ctypes.c_float * max(1, len(o.params)))(*o.params)
+            return c(L.pt_object_device_spans(h, o.spans_body.encode(), o.normal_body.encode(), prm, len(o.params),
+                                              o.max_spans, self._material(o.material)))
         if isinstance(o, (Union, Intersection, Difference)):
             op = {Union: 0, Intersection: 1, Difference: 2}[type(o)]
             a = self._obj(o.a)

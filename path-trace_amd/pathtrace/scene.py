@@ -339,6 +339,28 @@ class DeviceObject(Object):
         return DeviceObject(self.span_body, self.normal_body, self.params, self.material, self.oracle_slot)
 
 
+class DeviceSpansObject(Object):
+    """A user-defined Object subclass (reference include/object.h:14-20) whose
+    span iterator yields up to `max_spans` spans per ray (include/span.h:129-171),
+    given as device source (pt_object_device_spans): `spans_body` is the body
+    of int spans(V3 o, V3 d, float *t0, float *t1) -- the number of spans,
+    ordered and strictly separated, t0[k] <= t1[k] < t0[k + 1] --, `normal_body`
+    the body of V3 normal(V3 p, int k), the outward normal at boundary point p of
+    span k; both read `params` as `const float *prm`.  max_spans is
+    1..PT_OBJECT_MAX_SPANS (8).  The text scene format has no record for it."""
+    kind = "userspans"
+
+    def __init__(self, spans_body: str, normal_body: str, params, material: Material, max_spans: int):
+        self.spans_body = spans_body
+        self.normal_body = normal_body
+        self.params = [float(v) for v in params]
+        self.material = material
+        self.max_spans = int(max_spans)
+
+    def duplicate(self):
+        return DeviceSpansObject(self.spans_body, self.normal_body, self.params, self.material, self.max_spans)
+
+
 class Plane(Object):
     """Half-space {p : normal.p + d < 0} (src/plane.cpp:23-63).  Plane(n, d, m)
     or Plane(n, point, m) with d = -dot(n, point) (src/plane.cpp:11-14)."""
@@ -478,6 +500,8 @@ class _Registry:
         elif isinstance(o, DeviceObject):  # the oracle's host functions for the slot, the material, the parameters
             args = "%d %d %d %s" % (o.oracle_slot, self.material(o.material), len(o.params),
                                     " ".join(_hex(v) for v in o.params))
+        elif isinstance(o, DeviceSpansObject):
+            raise ValueError("DeviceSpansObject has no record in the text scene format")
         elif isinstance(o, _Binary):
             a = self.obj(o.a)
             b = self.obj(o.b)
