@@ -509,6 +509,7 @@ struct Stats
 {
     uint64_t queries = 0, sphere_tests = 0, sphere_hits = 0, plane_tests = 0, merge_steps = 0, shaded = 0,
              refract_children = 0, scatter_children = 0, attempts = 0, draws = 0, leaf_children = 0;
+    uint64_t cap_returns = 0; /* traceRay calls ended by the count > 1000 early return */
     uint64_t tex[7] = {0, 0, 0, 0, 0, 0, 0}; /* texture evaluations by class (TexCount) */
     void add(const Stats &o)
     {
@@ -517,6 +518,7 @@ struct Stats
         plane_tests += o.plane_tests, merge_steps += o.merge_steps, shaded += o.shaded;
         refract_children += o.refract_children, scatter_children += o.scatter_children;
         attempts += o.attempts, draws += o.draws, leaf_children += o.leaf_children;
+        cap_returns += o.cap_returns;
     }
 };
 
@@ -1132,6 +1134,7 @@ struct Tracer
                 do {
                     count++;
                     if (count > 1000) { /* path-trace.h:148-152 (NDEBUG semantics) */
+                        st.cap_returns++;
                         run.flush(retval);
                         return retval;
                     }
@@ -1348,7 +1351,7 @@ int oracle_render_adaptive(const char *scene_text, int W, int H, int spp, int de
 /* stats[0..10]: queries sphere_tests sphere_hits plane_tests merge_steps shaded
  * refract_children scatter_children attempts draws leaf_children; stats[11..17]:
  * texture evaluations (TexCount: xform multiply image spherical mirrorball
- * skybox log) -- the caller's array holds 18 */
+ * skybox log); stats[18]: cap_returns -- the caller's array holds 19 */
 int oracle_render_gw(const char *scene_text, int W, int H, int gw, int spp, int depth, float sw, float sh,
                      float dist, uint64_t seed, const int32_t *pixels, int npx, int threads, int order,
                      int per_sample, float *out, uint64_t *stats);
@@ -1418,6 +1421,7 @@ int oracle_render_gw(const char *scene_text, int W, int H, int gw, int spp, int 
                               total.scatter_children, total.attempts,         total.draws,
                               total.leaf_children};
             memcpy(stats, v, sizeof(v));
+            stats[18] = total.cap_returns;
         }
         return 0;
     } catch (std::exception &e) {
@@ -1431,14 +1435,28 @@ int oracle_render_gw(const char *scene_text, int W, int H, int gw, int spp, int 
  * spp samples in `order` (pixel_sum), sample s drawing from the engine keyed
  * (seed, ray_begin + ray index, sample_begin + s), each sample (0 + c) / 1 as a one-sample
  * tracePixel adds it, divided by spp -- what pt_trace_rays computes. */
+int oracle_trace_rays_stats(const char *scene_text, const float *rays, int n, int spp, int depth, uint64_t seed,
+                            int sample_begin, int64_t ray_begin, int threads, int order, float *out,
+                            uint64_t *stats);
+
 int oracle_trace_rays(const char *scene_text, const float *rays, int n, int spp, int depth, uint64_t seed,
                       int sample_begin, int64_t ray_begin, int threads, int order, float *out)
+{
+    return oracle_trace_rays_stats(scene_text, rays, n, spp, depth, seed, sample_begin, ray_begin, threads, order, out,
+                                   nullptr);
+}
+
+/* the same; stats (may be null): [0] queries, [1] cap_returns */
+int oracle_trace_rays_stats(const char *scene_text, const float *rays, int n, int spp, int depth, uint64_t seed,
+                            int sample_begin, int64_t ray_begin, int threads, int order, float *out,
+                            uint64_t *stats)
 {
     try {
         std::unique_ptr<Scene> scene = load_scene(scene_text);
         std::atomic<int> next(0);
         std::mutex mu;
         std::string err;
+        Stats total;
         auto worker = [&]() {
             Tracer<SampleEngine> tr(*scene, order == 1 ? ORDER_FAST : ORDER_REFERENCE);
             try {
@@ -1460,12 +1478,16 @@ int oracle_trace_rays(const char *scene_text, const float *rays, int n, int spp,
                 std::lock_guard<std::mutex> g(mu);
                 err = e.what();
             }
+            std::lock_guard<std::mutex> g(mu);
+            total.add(tr.st);
         };
         std::vector<std::thread> pool;
         for (int t = 0; t < (threads < 1 ? 1 : threads); t++) pool.emplace_back(worker);
         for (auto &t : pool) t.join();
         if (!err.empty())
             throw std::runtime_error(err);
+        if (stats)
+            stats[0] = total.queries, stats[1] = total.cap_returns;
         return 0;
     } catch (std::exception &e) {
         g_err = e.what();

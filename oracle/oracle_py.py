@@ -26,7 +26,9 @@ ORDER_FAST = 1
 STAT_NAMES = ["queries", "sphere_tests", "sphere_hits", "plane_tests", "merge_steps", "shaded",
               "refract_children", "scatter_children", "attempts", "draws", "leaf_children",
               # texture evaluations by class (oracle.cpp TexCount)
-              "tex_xform", "tex_multiply", "tex_image", "tex_spherical", "tex_mirrorball", "tex_skybox", "tex_log"]
+              "tex_xform", "tex_multiply", "tex_image", "tex_spherical", "tex_mirrorball", "tex_skybox", "tex_log",
+              # traceRay calls the count > 1000 early return ended (include/path-trace.h:144-157)
+              "cap_returns"]
 
 _lib = None
 
@@ -67,6 +69,8 @@ def lib():
         L.oracle_trace_rays.restype = C.c_int
         L.oracle_trace_rays.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
                                         C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_trace_rays_stats.restype = C.c_int
+        L.oracle_trace_rays_stats.argtypes = L.oracle_trace_rays.argtypes + [C.c_void_p]
         L.oracle_register_user_object.restype = ctypes.c_int
         L.oracle_register_user_object.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.oracle_register_user_texture.restype = ctypes.c_int
@@ -130,15 +134,20 @@ def render_adaptive(scene_text: str, W: int, H: int, spp: int, depth: int, block
 
 
 def trace_rays(scene_text: str, rays: np.ndarray, spp: int, depth: int, seed: int = 0x5EED, sample_begin: int = 0,
-               threads: int = 0, order: int = ORDER_REFERENCE, ray_begin: int = 0):
+               threads: int = 0, order: int = ORDER_REFERENCE, ray_begin: int = 0, stats: bool = False):
     """traceRay per caller ray (n x 7: origin, direction, strength): the mean
-    of spp samples keyed (seed, ray, sample) -- pt_trace_rays' restatement."""
+    of spp samples keyed (seed, ray, sample) -- pt_trace_rays' restatement.
+    With stats, also {"queries", "cap_returns"} summed over the batch."""
     r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
     out = np.zeros((len(r), 3), dtype=np.float32)
-    rc = lib().oracle_trace_rays(scene_text.encode(), r.ctypes.data, len(r), spp, depth, seed, sample_begin,
-                                 ray_begin, threads or (os.cpu_count() or 1), order, out.ctypes.data)
+    st = np.zeros(2, dtype=np.uint64)
+    rc = lib().oracle_trace_rays_stats(scene_text.encode(), r.ctypes.data, len(r), spp, depth, seed, sample_begin,
+                                       ray_begin, threads or (os.cpu_count() or 1), order, out.ctypes.data,
+                                       st.ctypes.data)
     if rc != 0:
         raise RuntimeError("oracle_trace_rays: " + lib().oracle_last_error().decode())
+    if stats:
+        return out, {"queries": int(st[0]), "cap_returns": int(st[1])}
     return out
 
 

@@ -1677,6 +1677,32 @@ struct Occl<Uni<A, B>>
     }
 };
 
+/* How often the reference negates the normal of a boundary of primitive `prim`
+ * on its way up through node N: a Difference hands A's boundaries through and
+ * takes B's by copyEndFromStart / copyStartFromEnd (src/difference.cpp:113-128),
+ * which negate (span.h:100-112); no other node does.  So the count is a fact of
+ * the tree: the Difference nodes of N that have the primitive on their B side. */
+template <class N>
+struct BFlips
+{
+    __device__ static constexpr int of(int) { return 0; }
+};
+template <class A, class B>
+struct BFlips<Uni<A, B>>
+{
+    __device__ static constexpr int of(int prim) { return prim < A::HI ? BFlips<A>::of(prim) : BFlips<B>::of(prim); }
+};
+template <class A, class B>
+struct BFlips<Isect<A, B>>
+{
+    __device__ static constexpr int of(int prim) { return prim < A::HI ? BFlips<A>::of(prim) : BFlips<B>::of(prim); }
+};
+template <class A, class B>
+struct BFlips<Diff<A, B>>
+{
+    __device__ static constexpr int of(int prim) { return prim < A::HI ? BFlips<A>::of(prim) : 1 + BFlips<B>::of(prim); }
+};
+
 template <int MOFF, int IOFF, class C>
 struct Xf
 {
@@ -1727,6 +1753,17 @@ struct Xf
     __device__ static __forceinline__ V3 normal(int prim, float t, V3 o, V3 d, const Env &e)
     {
         V3 n = C::normal(prim, t, m_apply(e.P + MOFF, o), m_lin(e.P + MOFF, d), e);
+        /* The caller negates once for the FLIP parity of the whole path.  The
+         * negations of the Differences below this node happen before the
+         * mapping in the reference, and M(-n) is -M(n) except in the sign of a
+         * zero sum (x * 0 terms of either sign, exact cancellation): take them
+         * here, and out again so that the caller's negation stays right. */
+        if constexpr (!C::NO_DIFF) {
+            const bool neg = BFlips<C>::of(prim) & 1;
+            n = neg ? -n : n;
+            n = PT_NORM(m_lin(e.P + IOFF, n));
+            return neg ? -n : n;
+        }
         return PT_NORM(m_lin(e.P + IOFF, n));
     }
     /* no raw-direction dark test through a transform unless nothing inside is selected */
@@ -1738,6 +1775,11 @@ struct Xf
     __device__ static __forceinline__ u64 dark_mask(const Ctx &, V3, const Env &) { return ~0ull; }
     template <class SEL>
     __device__ static __forceinline__ bool dark_pre(const Ctx &, const Env &) { return true; }
+};
+template <int MOFF, int IOFF, class C>
+struct BFlips<Xf<MOFF, IOFF, C>>
+{
+    __device__ static constexpr int of(int prim) { return BFlips<C>::of(prim); }
 };
 
 /* First qualifying span of the root, traceRay's scan (path-trace.h:66-100). */

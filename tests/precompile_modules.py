@@ -45,7 +45,23 @@ def test_jobs():
     # tests/test_occlude.py: plane occluders near the emitters
     from test_occlude import VARIANTS as OC_VARIANTS, DEPTH as OC_DEPTH
     jobs += [((lambda v=v: pt.DeviceScene(zoo.occlude_box(v))), OC_DEPTH) for v in OC_VARIANTS]
-    return jobs
+    return jobs + csgfuzz_jobs()
+
+
+def csgfuzz_jobs():
+    """tests/test_csgfuzz.py: the ray-list modules of the trace scenes and of the cap scene, the cap
+    render, then a span-query module per tree (long compiles first)"""
+    import pathtrace as pt
+    import csgfuzz as F
+    from pathtrace.scene import to_text
+    from test_csgfuzz import CAP_OPTS, TRACE_DEPTH
+    rays = [(lambda s=s, o=o: pt.DeviceScene(F.trace_scene(s), **o).compile_rays(TRACE_DEPTH), None)
+            for s in range(F.N_TRACE_SCENES) for o in [{}] + (F.MODE_OPTS if s in F.mode_scenes() else [])]
+    rays += [(lambda o=o: pt.DeviceScene(F.cap_scene(), **o).compile_rays(F.CAP_DEPTH), None) for o in CAP_OPTS]
+    render = [((lambda: pt.DeviceScene(F.cap_scene(F.CAP_RENDER["shift"]))), F.CAP_RENDER["depth"])]
+    spans = [(lambda b=b: pt.DeviceScene.from_text(to_text(b())).compile_queries(), None)
+             for (_, b) in F.span_trees()]
+    return rays + render + spans
 
 
 def _rays(builder, opts):

@@ -42,7 +42,8 @@ SKIES = {
     "overflow": lambda: MultiplyTexture((1e30, 1.0, 1.0), ColorTexture((1e20, 0.7, 1.0))),
 }
 # (sky, lane_walk) of the GPU cases (tests/precompile_modules.py builds their modules)
-CASES = [("finite", 0), ("inf", 0), ("overflow", 0), ("finite", 2), ("inf", 2)]
+# lane_walk=1 is what config C5 ships: its mode-3 deferred skip runs here too
+CASES = [("finite", 0), ("inf", 0), ("overflow", 0), ("finite", 2), ("inf", 2), ("finite", 1), ("inf", 1)]
 W, H, SPP, DEPTH = 40, 24, 4, 5
 
 
