@@ -807,6 +807,37 @@ const int DefaultRayDepth = 16;          /* include/path-trace.h:57  */
 const int DefaultSampleCount = 200;      /* include/path-trace.h:167 */
 const float DefaultScreenWidth = 4.0 / 3.0, DefaultScreenHeight = 1.0, DefaultScreenDistance = 2.0; /* :168-170 */
 
+/* The reference's DefaultRandomEngine (include/path-trace.h:21-54) with its
+ * public members: the 64-bit LCG v = 214013 v + 2531011, output v >> 32,
+ * seed(s) setting v = s ^ 0x12476242.  state() is the one extension: the
+ * engine's v, for saving and restoring a stream.  Passed to tracePixel /
+ * traceRay it is an engine type T like any other (two of its draws seed the
+ * call, below): the device does not yet run a call's samples draw by draw on
+ * the caller's state, which is what the reference does with this engine. */
+class DefaultRandomEngine
+{
+public:
+    DefaultRandomEngine() { seed(0); }
+    static unsigned min() { return 0; }
+    static unsigned max() { return 0xFFFFFFFF; }
+    void seed(unsigned newValue) { v = newValue ^ 0x12476242; }
+    unsigned operator()()
+    {
+        v = (214013 * v + 2531011);
+        return (unsigned)(v >> 32);
+    }
+    void discard(unsigned long long count)
+    {
+        for (unsigned long long i = 0; i < count; i++)
+            operator()();
+    }
+    uint64_t state() const { return v; }
+    void state(uint64_t newState) { v = newState; }
+
+private:
+    uint64_t v;
+};
+
 /* The engine argument of tracePixel (include/path-trace.h:187-201 takes the
  * caller's `T &randomEngine` and draws every sample of every pixel from it in
  * sequence).  The device gives each (pixel, sample) an engine of its own,

@@ -27,7 +27,7 @@ from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject,
                     transform_material, transform_object, transform_texture, union_array)
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["DeviceScene", "render", "render_device", "prepare",
-                                                         "trace_rays"]
+                                                         "trace_rays", "lcg_state"]
 
 ORDERS = {"fast": PT_ORDER_FAST, "reference": PT_ORDER_REFERENCE,
           "strict": PT_ORDER_REFERENCE,
@@ -276,6 +276,12 @@ def trace_rays(scene, rays, depth: int, spp: int = 1, seed: int = 0x5EED, order=
     _lib.check(_lib.lib().pt_trace_rays(ds.handle, ctypes.byref(tp), r.ctypes.data, len(r), out.ctypes.data,
                                         ctypes.byref(st)))
     return (out, st.as_dict()) if stats else out
+
+
+def lcg_state(seed: int) -> int:
+    """The state of the reference's DefaultRandomEngine after seed(seed)
+    (include/path-trace.h:36-39): the 64-bit v its recurrence starts from."""
+    return (int(seed) & 0xFFFFFFFF) ^ 0x12476242
 
 
 def render_adaptive(scene, width: int, height: int, spp: int, depth: int, screen=None, seed: int = 0x5EED,
