@@ -214,6 +214,7 @@ typedef struct pt_render_stats {
     uint64_t mid_queries;          /* leaf children the clear pass could not finish (fast check) */
     double wave_ms;                /* mean render-wave lifetime (device clock); kernel_ms minus
                                       this is the launch's tail, where waves have run out of work */
+    uint64_t shaded;               /* traceRay activations that shade their hit (depth and strength left) */
 } pt_render_stats;
 
 /* Synchronous: renders the frame into rgb_out (host memory), which receives,
@@ -371,6 +372,16 @@ int pt_scene_set_lane_walk(pt_scene *s, int frames);
  * dozen leaves each); supersedes pt_scene_set_lane_walk.  Takes effect at the
  * next compile/render. */
 int pt_scene_set_lane_scatter(pt_scene *s, int on);
+/* MI355X tuning knob, no reference counterpart: each lane of a chunk keeps its
+ * sample and walks the whole ray tree; at a scatter loop it suspends, the wave
+ * runs that one burst for it and hands back the sum and the advanced engine
+ * state, and the lane resumes.  The wave never walks a sample's spine (same
+ * bits either way).  Applies where no burst can end in a recursing child
+ * (pt_scene_reach_facts: bursts_all_leaf) and neither pt_scene_set_lane_walk
+ * nor pt_scene_set_lane_scatter is chosen; asked for elsewhere, the module is
+ * built without it.  1 = on, 0 = off, -1 = auto (the default).  Takes effect
+ * at the next compile/render. */
+int pt_scene_set_lane_resume(pt_scene *s, int on);
 /* MI355X tuning knob, no reference counterpart: lane-walk scenes render in
  * split launches (default on) -- a light kernel (no lazy merges, no wave walk,
  * higher occupancy) over every chunk, then the full kernel over the chunks

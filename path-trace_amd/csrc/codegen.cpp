@@ -412,6 +412,11 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     Gen g(s);
     int axis_share = 0;
     const std::string root = g.shared_axes(g.obj(s.root), axis_share);
+    /* kr_reach, bursts_all_leaf: the burst variants the materials can reach
+     * (Gen::reach_facts; pt_device.h PT_REACH_PRUNE instantiates only those) */
+    int kr_reach = 0;
+    bool bursts_all_leaf = false;
+    g.reach_facts(kr_reach, bursts_all_leaf);
 
     /* material dispatchers; texture params are appended after geometry */
     struct MatTypes
@@ -481,6 +486,15 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     /* per-scene lane walk with scatter loops (pt_scene_set_lane_scatter) */
     if (s.lane_scatter)
         src << "#define PT_LANE_SCATTER 1\n";
+    /* per-scene resumable lane walk (pt_scene_set_lane_resume): lanes walk
+     * their whole trees and ask the wave for each burst.  Only where no burst
+     * can end in a recursing child and no other lane walk is chosen; asked
+     * for elsewhere, the module is built without it.  Auto (-1) follows
+     * LANE_RESUME_AUTO, decided by the C3 measurement */
+    constexpr bool LANE_RESUME_AUTO = true;
+    if ((s.lane_resume < 0 ? LANE_RESUME_AUTO : s.lane_resume > 0) && bursts_all_leaf && s.lane_walk == 0 &&
+        !s.lane_scatter)
+        src << "#define PT_LANE_RESUME 1\n";
     /* Difference-free trees skip a sphere's root and divisions when no lane of
      * the wave meets it (pt_device.h PT_SPHERE_SKIP; same-box A/B,
      * profiles/round4/ab_sphere_skip.txt: C2 +7.2 %, C5 +0.3 %, C3 -10 %) */
@@ -556,11 +570,6 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     for (size_t k = 0; k < g.mats.size() && emis_finite; k++)
         emis_finite = g.color_bound(s.materials.at(g.mats[k]).emissive) <= (double)FLT_MAX;
     src << "  static constexpr bool emis_finite = " << (emis_finite ? "true" : "false") << ";\n";
-    /* kr_reach, bursts_all_leaf: the burst variants the materials can reach
-     * (Gen::reach_facts; pt_device.h PT_REACH_PRUNE instantiates only those) */
-    int kr_reach = 0;
-    bool bursts_all_leaf = false;
-    g.reach_facts(kr_reach, bursts_all_leaf);
     src << "  static constexpr int kr_reach = " << kr_reach << ";\n";
     src << "  static constexpr bool bursts_all_leaf = " << (bursts_all_leaf ? "true" : "false") << ";\n";
     if (all_emis_const && lit_mats.size() <= 4) {

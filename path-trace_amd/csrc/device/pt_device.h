@@ -2550,6 +2550,7 @@ struct Counters
     u64 ch[3]; /* cycles of the chunk loop: all of it, the lane-parallel front end, the result writes */
     u64 sp[3]; /* the spine's span queries: cycles, count, those that ran the lazy merge */
     u64 np[8]; /* events: bursts, loop iterations, (unused), fast passes, slow passes, accumulations, fast lanes, slow lanes */
+    u64 rs[2]; /* PT_LANE_RESUME, cycles: the lanes' walk steps, the service overhead (request copy, engine hand-over, hand-back) */
 #define PT_CNT(c, k, v) (c).np[k] += (v)
 #else
 #define PT_CNT(c, k, v)
@@ -4580,6 +4581,177 @@ __device__ __forceinline__ V3 trace_sample(const Env &e, const PtLaunch &lp, int
     return (z + result) / 1.0f;
 }
 
+#ifdef PT_LANE_RESUME
+/* A whole sample kept by its lane, the wave serving its bursts (scenes whose
+ * bursts end in leaves only: Reach<S>::all_leaf, so burst() is one call from
+ * (hit, n, refl, rc, sc, strength, add, depth, N, i = 0, retval, engine) to
+ * (retval, engine)).  The lane walks its tree depth first with the spine's own
+ * statements (trace_sample PH_ENTER / PH_SETUP / PH_LOOP / PH_RETURN, the fold
+ * retval = (e + w_R r_R) + w_M r_M, the zero-weight child rule).  At a scatter
+ * loop (sc > eps) it completes PH_SETUP per lane, pushes the burst's request
+ * as its top frame and suspends; render_chunk's service loop runs burst() for
+ * it and writes the sum back into that frame's `part`, and the walk goes on
+ * at PH_RETURN.  Scatter-free nodes draw nothing, so the engine state a burst
+ * receives is the one trace_sample would have reached.
+ *
+ * Nothing of the walk stays in registers across a service: nodes are a
+ * per-lane frame array in the private segment indexed by sp (a node of depth
+ * budget dep sits at index depth - dep and is shaded only for dep >= 1, so
+ * MAXD + 1 entries hold every walk), and a walk starts, like it resumes, by
+ * popping its top frame -- render_chunk pushes the sample's ray as a RS_START
+ * frame. */
+struct RsFrame
+{
+    V3 hit, n, a, part, w, rc; /* a: incoming direction; a burst request's reflected direction */
+    float str, rf, sc, add;
+    int dep, ms, N;            /* ms: material << 2 | stage; N: the burst's children (RS_START: camera hit | exit << 1) */
+};
+enum { RS_AFTER_R = 0, RS_AFTER_M = 1, RS_BURST = 2, RS_START = 3 };
+enum { RS_DONE = 0, RS_RUN = 1, RS_SUSPENDED = 2 };
+/* runs the lane's walk from its top frame until it is done (res) or
+ * suspended at a burst; nq / nsh += queries / shaded nodes */
+template <class S>
+__device__ __forceinline__ int lane_walk_rs(const Env &e, RsFrame *F, int &sp, V3 &res, int &nq, int &nsh)
+{
+    enum { ENTER, SETUP, RETURN };
+    /* the node being shaded is F[sp], written in place: a push is sp++ */
+    int state = RETURN;
+    V3 o = mk(0, 0, 0), d = mk(0, 0, 0), r = mk(0, 0, 0);
+    int dep = 0;
+    float str = 0.0f;
+    CamHit ch = {0, 0.0f, 0u, 0};
+    bool first = false;
+    for (;;) {
+        if (state == ENTER) {
+            nq++;
+            float t = 0.0f;
+            u32 ref = 0;
+            bool ex = false, found;
+            if (first) {
+                found = ch.hit != 0, t = ch.t, ref = ch.ref, ex = ch.ex != 0;
+                first = false;
+            } else {
+                typename S::Root::Ctx ctx;
+                S::Root::prep_l(ctx, o, e);
+                found = lane_first_hit<typename S::Root>(ctx, d, e, t, ref, ex);
+            }
+            if (!found) {
+                r = mk(0, 0, 0);
+                state = RETURN;
+                continue;
+            }
+            const V3 hit = o + t * d;
+            const int mat = ref_mat(ref);
+            V3 nn = S::Root::normal(ref_prim(ref), t, o, d, e);
+            if (ref & FLIP)
+                nn = -nn;
+            float ior;
+            V3 n;
+            if (ex) {
+                n = -nn;
+                ior = S::ior(mat, e);
+            } else {
+                n = nn;
+                ior = (float)(1.0 / (double)S::ior(mat, e));
+            }
+            const V3 retval = S::emis(mat, hit, e);
+            if (dep <= 0 || str < EPS) {
+                r = retval;
+                state = RETURN;
+                continue;
+            }
+            nsh++;
+            RsFrame &c = F[sp];
+            c.hit = hit, c.n = n, c.a = d, c.part = retval, c.str = str, c.dep = dep, c.add = 1.0f;
+            const float rf = clamp01(S::trc(mat, hit, e)) * refract_strength(d, ior, n);
+            c.rf = rf;
+            c.ms = mat << 2;
+            state = SETUP;
+            if (rf > EPS) {
+                const V3 rd = refract(d, ior, n);
+                if (!is_zero(rd)) {
+                    const V3 tr = S::trans(mat, hit, e);
+                    c.w = (1.0f * rf) * tr; /* addFactor * refractFactor * transmit */
+                    c.ms = (mat << 2) | RS_AFTER_R;
+                    sp++;
+                    o = hit, d = rd, str = str * rf * 1.0f * length(tr), dep = dep - 1;
+                    state = ENTER;
+                }
+            }
+        } else if (state == SETUP) {
+            RsFrame &c = F[sp];
+            const float add = c.add;
+            const V3 part = c.part;
+            if (add < EPS) {
+                r = part;
+                state = RETURN;
+                continue;
+            }
+            const int mat = c.ms >> 2;
+            const V3 hit = c.hit, n = c.n;
+            const float cstr0 = c.str;
+            const int cdep = c.dep;
+            const float sc = clamp01(S::scat(mat, hit, e));
+            int N = cvt_x86(10000.0f * cstr0 * add * sc);
+            if (sc <= EPS)
+                N = 1;
+            if (N == 0)
+                N = 1;
+            const V3 rc = S::refl(mat, hit, e);
+            const V3 refl = reflect(c.a, n);
+            if (Reach<S>::kr != 0 && sc > EPS) { /* a scatter loop: the wave's burst, asked for */
+                c.rc = rc, c.a = refl, c.sc = sc, c.N = N;
+                c.ms = (mat << 2) | RS_BURST;
+                sp++;
+                return RS_SUSPENDED;
+            }
+            /* PH_LOOP's single mirror child */
+            const float Nf = (float)N;
+            const float factor = 1.0f - (1.0f - dot(refl, n)) * sc;
+            const V3 w = ((add / Nf) * factor) * rc;
+            const float cstr = (((cstr0 / Nf) * add) * factor) * length(rc);
+#if PT_ZERO_CHILD
+            if constexpr (S::emis_finite)
+                if (zero_child(w, cstr, cdep - 1, part)) {
+                    nq++; /* the child's query, skipped */
+                    r = part;
+                    state = RETURN;
+                    continue;
+                }
+#endif
+            c.w = w;
+            c.ms = (mat << 2) | RS_AFTER_M;
+            sp++;
+            o = hit, d = refl, str = cstr, dep = cdep - 1;
+            state = ENTER;
+        } else { /* RETURN: fold the finished child into the top frame */
+            if (sp == 0)
+                break;
+            RsFrame &c = F[--sp];
+            const int stage = c.ms & 3;
+            if (stage == RS_AFTER_R) {
+                c.part = c.part + c.w * r;
+                c.add = 1.0f * (1.0f - c.rf);
+                state = SETUP;
+            } else if (stage == RS_AFTER_M) {
+                r = c.part + c.w * r;
+            } else if (stage == RS_BURST) {
+                r = c.part; /* the burst's retval (B_DONE and B_ABORT alike) */
+            } else { /* RS_START: the sample's ray and its camera query */
+                o = c.hit, d = c.a, str = c.str, dep = c.dep;
+                ch.hit = c.N & 1, ch.ex = (c.N >> 1) & 1, ch.t = c.rf, ch.ref = __float_as_uint(c.sc);
+                first = true;
+                state = ENTER;
+            }
+        }
+    }
+    /* tracePixel with one sample: (Color(0,0,0) + traceRay(...)) / 1 */
+    const V3 z = mk(0, 0, 0);
+    res = (z + r) / 1.0f;
+    return RS_DONE;
+}
+#endif
+
 #ifndef PT_WPW
 #define PT_WPW 4 /* independent waves per workgroup */
 #endif
@@ -4700,6 +4872,16 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
     const int wave = SCALAR_WAVE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
     const u64 t_start = __builtin_amdgcn_s_memrealtime(); /* 100 MHz: wave lifetimes, stats[26..29] */
+#ifdef PT_LANE_RESUME
+#if defined(PT_LANE_WALK) || defined(PT_LANE_SCATTER)
+#error "PT_LANE_RESUME excludes PT_LANE_WALK and PT_LANE_SCATTER"
+#endif
+    /* lanes keep their samples and the wave serves their bursts (lane_walk_rs) */
+    constexpr bool RESUME = Reach<S>::all_leaf && !LIGHT;
+    RsFrame RF[RESUME ? MAXD + 1 : 1];
+#else
+    constexpr bool RESUME = false;
+#endif
     const Env e = {P, imgs};
 #ifdef PT_POISON_LDS
     /* test build: every LDS word starts as all-ones (NaN floats, ring numbers
@@ -4734,6 +4916,7 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
         cnt.np[k] = 0;
     cnt.sp[0] = cnt.sp[1] = cnt.sp[2] = 0;
     cnt.ch[0] = cnt.ch[1] = cnt.ch[2] = 0;
+    cnt.rs[0] = cnt.rs[1] = 0;
 #endif
     const WaveLds L = {&xbuf[wave], rbuf[wave], sbuf[wave], mbuf[wave], LSUM_LDS ? lsbuf[wave] : nullptr,
                        stbuf[wave], smbuf[wave]};
@@ -4817,6 +5000,8 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
         CamHit ch = {0, 0.0f, 0u, 0};
         int ldone = 0, lq = 0, lsh = 0;
         int lpix = 0, ls = 0; /* the lane's (pixel, sample), read by the wave loop below */
+        [[maybe_unused]] int rsp = 0; /* PT_LANE_RESUME: the lane's frames */
+        [[maybe_unused]] u64 lrng = 0; /* ... and its engine after the camera draws */
         V3 lres = mk(0, 0, 0);
         const bool lvalid = lane < CH && item0 + lane < lp.n_items;
         if (lvalid) {
@@ -4858,6 +5043,17 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
             ldone = lane_walk<S>(e, lp.depth, o, d, str, ch, lres, lq, lsh) ? 1 : 0;
 #else
             ldone = lane_sample<S>(e, lp.depth, o, d, str, ch, lres, lq, lsh) ? 1 : 0;
+#ifdef PT_LANE_RESUME
+            if constexpr (RESUME)
+                if (!ldone) { /* the walk starts from this frame */
+                    RsFrame &w = RF[0];
+                    w.hit = o, w.a = d, w.str = str, w.dep = lp.depth;
+                    w.N = ch.hit | (ch.ex << 1), w.rf = ch.t, w.sc = __uint_as_float(ch.ref);
+                    w.ms = RS_START;
+                    rsp = 1;
+                    lrng = r.st;
+                }
+#endif
 #endif
             }
         }
@@ -4899,6 +5095,84 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
 #endif
         }
         V3 mine = lres;
+#ifdef PT_LANE_RESUME
+        if constexpr (RESUME) {
+            /* Every unfinished lane walks its own tree; the wave serves the
+             * bursts they suspend at, one after another in lane order (each
+             * sample has its own engine: the order changes no bit), until no
+             * lane is suspended.  A lane's slot of lbuf holds its engine and
+             * its counts (queries | shaded << 16) while it walks, then its
+             * result; across a service only its frame index and status stay
+             * in registers. */
+            uint4 *const lb = lbuf[wave];
+            PT_T0(tt);
+            int st = lvalid && !ldone ? RS_RUN : RS_DONE;
+            lb[lane] = st == RS_RUN
+                           ? make_uint4((u32)lrng, (u32)(lrng >> 32), 0u, 0u)
+                           : make_uint4(__float_as_uint(lres.x), __float_as_uint(lres.y), __float_as_uint(lres.z), 0u);
+            for (;;) {
+                PT_T0(tw);
+                if (st == RS_RUN) {
+                    V3 wr = mk(0, 0, 0);
+                    int q = 0, h = 0;
+                    st = lane_walk_rs<S>(e, RF, rsp, wr, q, h);
+                    const u32 n = lb[lane].z + ((u32)q | ((u32)h << 16));
+                    if (st == RS_DONE)
+                        lb[lane] = make_uint4(__float_as_uint(wr.x), __float_as_uint(wr.y), __float_as_uint(wr.z), n);
+                    else
+                        lb[lane].z = n;
+                }
+#ifdef PT_PHASE_TIMING
+                cnt.rs[0] += __builtin_amdgcn_s_memtime() - tw;
+#endif
+                u64 SM = __ballot(st == RS_SUSPENDED);
+                if (!SM)
+                    break;
+                Frame &f = stk[wave][0];
+                for (; SM; SM &= SM - 1) {
+                    const int j = uni(__builtin_ctzll(SM));
+                    PT_T0(ts);
+                    if (lane == j) { /* the request: the lane's top frame */
+                        const RsFrame &q = RF[rsp - 1];
+                        f.hit = q.hit, f.n = q.n, f.rc = q.rc, f.refl = q.a, f.sc = q.sc, f.strength = q.str;
+                        f.add = q.add, f.depth = q.dep, f.N = q.N, f.i = 0, f.retval = q.part;
+                    }
+                    /* one lane wrote what every lane reads: without the fence the
+                     * compiler may forward each lane's own (stale) view of f */
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    const uint4 qe = lb[j];
+                    Rng rng;
+                    rng.st = ((u64)(u32)uni((int)qe.y) << 32) | (u64)(u32)uni((int)qe.x);
+#ifdef PT_PHASE_TIMING
+                    cnt.rs[1] += __builtin_amdgcn_s_memtime() - ts;
+#endif
+                    burst<S, STRICT>(e, rng, jump, jl, L, f, stk[wave][1], cnt);
+                    PT_T0(tb);
+                    if (lane == j) { /* the sum and the advanced engine go back */
+                        const V3 rv = f.retval;
+                        RF[rsp - 1].part = rv;
+                        lb[j].x = (u32)rng.st, lb[j].y = (u32)(rng.st >> 32);
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#ifdef PT_PHASE_TIMING
+                    cnt.rs[1] += __builtin_amdgcn_s_memtime() - tb;
+#endif
+                }
+                if (st == RS_SUSPENDED)
+                    st = RS_RUN;
+            }
+            const uint4 mr = lb[lane];
+            mine = mk(__uint_as_float(mr.x), __uint_as_float(mr.y), __uint_as_float(mr.z));
+            /* the walked samples' statistics: a wave sum of small integers */
+            int q = (int)(mr.w & 0xFFFFu), h = (int)(mr.w >> 16);
+#pragma unroll
+            for (int w = 32; w >= 1; w >>= 1)
+                q += __shfl_xor(q, w), h += __shfl_xor(h, w);
+            cnt.queries += (u64)(u32)uni(q);
+            cnt.shaded += (u64)(u32)uni(h);
+            PT_ACC(cnt, 6, tt);
+        } else
+#endif
         if constexpr (!LIGHT) {
         /* park the lanes' state in LDS for the walks below */
         uint4 *const lb = lbuf[wave];
@@ -5002,6 +5276,8 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
         atomicAdd(&stats[33], cnt.ch[2]);
         atomicAdd(&stats[31], cnt.sp[1]);
         atomicAdd(&stats[34], cnt.sp[2]);
+        atomicAdd(&stats[37], cnt.rs[0]);
+        atomicAdd(&stats[38], cnt.rs[1]);
 #endif
     }
 }

@@ -755,6 +755,7 @@ std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays)
     f.add(s.images.size());
     f.add(s.root), f.add(s.default_tex[0]), f.add(s.default_tex[1]);
     f.add(s.wg_per_cu), f.add(s.fast_spine), f.add(s.lane_walk), f.add(s.lane_scatter);
+    f.add(s.lane_resume);
     f.add(depth), f.add(rays);
     f.str(getenv("PT_DEVICE_DEFINES")), f.str(getenv("PT_JIT_OPTIONS"));
     auto it = s.gen_cache.find(f.h);
@@ -834,6 +835,7 @@ void collect_timings(DeviceState &ds, pt_render_stats *st)
     st->slow_queries = c[6];
     st->dark_queries = c[7];
     st->mid_queries = c[24];
+    st->shaded = c[4];
     if (c[29])
         st->wave_ms = (double)c[28] * (double)st->launches / (double)c[29] / 1e5; /* 100 MHz clock */
     if (getenv("PT_PHASE_DUMP")) /* profiling builds (PT_PHASE_TIMING): per-phase wave cycles */
@@ -847,6 +849,7 @@ void collect_timings(DeviceState &ds, pt_render_stats *st)
         fprintf(stderr, " %llu %llu", (unsigned long long)c[30], (unsigned long long)c[31]); /* spine queries */
         fprintf(stderr, " %llu %llu", (unsigned long long)c[32], (unsigned long long)c[33]); /* lane front end, writes */
         fprintf(stderr, " %llu", (unsigned long long)c[34]); /* spine queries that ran the lazy merge */
+        fprintf(stderr, " %llu %llu", (unsigned long long)c[37], (unsigned long long)c[38]); /* lane-resume walk steps, service overhead */
         fprintf(stderr, "\n");
     }
     st->sphere_tests = st->queries * (uint64_t)ds.pending.back().n_spheres;
@@ -1564,6 +1567,14 @@ int pt_scene_set_lane_scatter(pt_scene *s, int on)
     });
 }
 
+int pt_scene_set_lane_resume(pt_scene *s, int on)
+{
+    return guard([&] {
+        S(s).lane_resume = on < 0 ? -1 : on ? 1 : 0;
+        return PT_OK;
+    });
+}
+
 const char *pt_scene_kernel_key(pt_scene *s, int depth)
 {
     thread_local std::string k;
@@ -1946,6 +1957,7 @@ int pt_render_adaptive(pt_scene *s, const pt_render_params *p, pt_adaptive_param
             acc.attempts += st.attempts, acc.rounds += st.rounds, acc.slow_queries += st.slow_queries;
             acc.dark_queries += st.dark_queries, acc.mid_queries += st.mid_queries;
             acc.wave_ms += st.wave_ms; /* summed over the batches, like kernel_ms */
+            acc.shaded += st.shaded;
             ap->levels++;
             need.clear();
         };

@@ -39,7 +39,7 @@ class DeviceScene:
     constructors (one pt_* call per reference constructor)."""
 
     def __init__(self, root: Object, workgroups_per_cu: int = 0, fast_spine: bool = False, lane_walk: int = 0,
-                 lane_scatter: bool = False, split: bool = True):
+                 lane_scatter: bool = False, split: bool = True, lane_resume=None):
         L = _lib.lib()
         self._h = L.pt_scene_create()
         if not self._h:
@@ -54,6 +54,8 @@ class DeviceScene:
             _lib.check(L.pt_scene_set_lane_scatter(self._h, 1))
         if not split:
             _lib.check(L.pt_scene_set_split(self._h, 0))
+        if lane_resume is not None:  # None: the runtime's default (pt_scene_set_lane_resume's auto)
+            _lib.check(L.pt_scene_set_lane_resume(self._h, int(lane_resume)))
         self._img = {}
         self._mat = {}
         self.root = root

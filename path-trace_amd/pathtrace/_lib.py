@@ -48,7 +48,8 @@ class RenderStats(ctypes.Structure):
                 ("attempts", ctypes.c_uint64), ("rounds", ctypes.c_uint64), ("sphere_tests", ctypes.c_uint64),
                 ("sphere_hits", ctypes.c_uint64), ("plane_tests", ctypes.c_uint64),
                 ("slow_queries", ctypes.c_uint64), ("dark_queries", ctypes.c_uint64),
-                ("mid_queries", ctypes.c_uint64), ("wave_ms", ctypes.c_double)]
+                ("mid_queries", ctypes.c_uint64), ("wave_ms", ctypes.c_double),
+                ("shaded", ctypes.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -113,6 +114,7 @@ SIGNATURES = {
     "pt_scene_set_lane_walk": (_I, [_P, _I]),
     "pt_scene_set_split": (_I, [_P, _I]),
     "pt_scene_set_lane_scatter": (_I, [_P, _I]),
+    "pt_scene_set_lane_resume": (_I, [_P, _I]),
     "pt_scene_kernel_key": (ctypes.c_char_p, [_P, _I]),
     "pt_scene_reach_facts": (_I, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pt_selftest_math": (_I, [_I, ctypes.c_uint64, ctypes.c_uint64, _P]),

@@ -42,11 +42,19 @@ for line in r.stderr.splitlines():
             print("%-12s %6.1f%%  (%.0f cycles per query)" % ("spine-query", 100.0 * v[16] / tot, v[16] / v[17]))
             if len(v) >= 21:
                 print("%-12s %6.1f%%  of the spine's queries ran the lazy merge" % ("spine-merge", 100.0 * v[20] / v[17]))
+        if len(v) >= 23 and (v[21] or v[22]):
+            # lane-resume builds: "sample" is the walk-and-serve loop, so its "spine" row is lane walk + service + rest
+            print("%-12s %6.1f%%  the lanes' walk steps (lane resume)" % ("lane-walk", 100.0 * v[21] / tot))
+            print("%-12s %6.1f%%  request copy, engine hand-over, hand-back (%.0f cycles per burst)" %
+                  ("service", 100.0 * v[22] / tot, v[22] / (v[7] or 1)))
         if len(v) >= 15:
             import json as _j
             last = _j.loads(r.stdout.strip().splitlines()[-1])
             smp = last.get("samples") or last.get("samples_per_step")
             ev = ["bursts", "iterations", "stageA_passes", "fast_passes", "slow_passes", "group_sums",
                   "fast_lanes", "slow_lanes"]
+            if len(v) >= 16 and v[15]:
+                print("%-14s %10.1f wave-cycles per sample (chunk loop), %.1f in \"sample\", %.1f outside bursts" %
+                      ("wall", v[15] / smp, v[6] / smp, (v[6] - v[5]) / smp))
             for n, x in zip(ev, v[7:15]):
                 print("%-14s %10.3f per sample" % (n, x / smp))
