@@ -510,6 +510,9 @@ struct Stats
     uint64_t queries = 0, sphere_tests = 0, sphere_hits = 0, plane_tests = 0, merge_steps = 0, shaded = 0,
              refract_children = 0, scatter_children = 0, attempts = 0, draws = 0, leaf_children = 0;
     uint64_t cap_returns = 0; /* traceRay calls ended by the count > 1000 early return */
+    /* scatter loops with sc > eps that run (N > 0), and those of them entered by a traceRay call at
+     * recursion level >= 2 (a refraction or mirror child, not the caller's ray itself) */
+    uint64_t bursts = 0, nested_bursts = 0;
     uint64_t tex[7] = {0, 0, 0, 0, 0, 0, 0}; /* texture evaluations by class (TexCount) */
     void add(const Stats &o)
     {
@@ -519,6 +522,7 @@ struct Stats
         refract_children += o.refract_children, scatter_children += o.scatter_children;
         attempts += o.attempts, draws += o.draws, leaf_children += o.leaf_children;
         cap_returns += o.cap_returns;
+        bursts += o.bursts, nested_bursts += o.nested_bursts;
     }
 };
 
@@ -1047,6 +1051,7 @@ struct Tracer
     const Scene &scene;
     Order order;
     Stats st;
+    int level = 0; /* traceRay calls on the stack (the caller's ray runs at level 1) */
     Tracer(const Scene &s, Order o) : scene(s), order(o) {}
 
     float u(E &e, float lo, float hi)
@@ -1073,6 +1078,12 @@ struct Tracer
     /* traceRay<T>, include/path-trace.h:58-165 */
     V3 trace(const Ray &ray, int depth, E &rng, float strength)
     {
+        struct Level
+        {
+            int &l;
+            Level(int &v) : l(v) { l++; }
+            ~Level() { l--; }
+        } lv(level);
         st.queries++;
         SpanList l;
         scene.root->spans(ray, l, st);
@@ -1126,6 +1137,11 @@ struct Tracer
         V3 rc = mat->reflect->color(hit);
         LaneSums run;
         bool grouped = order == ORDER_FAST && sc > kEps;
+        if (sc > kEps && N > 0) {
+            st.bursts++;
+            if (level >= 2)
+                st.nested_bursts++;
+        }
         for (int i = 0; i < N; i++) {
             V3 refl = reflect(ray.d, n);
             V3 dir = refl;
@@ -1351,7 +1367,8 @@ int oracle_render_adaptive(const char *scene_text, int W, int H, int spp, int de
 /* stats[0..10]: queries sphere_tests sphere_hits plane_tests merge_steps shaded
  * refract_children scatter_children attempts draws leaf_children; stats[11..17]:
  * texture evaluations (TexCount: xform multiply image spherical mirrorball
- * skybox log); stats[18]: cap_returns -- the caller's array holds 19 */
+ * skybox log); stats[18]: cap_returns; stats[19..20]: bursts nested_bursts --
+ * the caller's array holds 21 */
 int oracle_render_gw(const char *scene_text, int W, int H, int gw, int spp, int depth, float sw, float sh,
                      float dist, uint64_t seed, const int32_t *pixels, int npx, int threads, int order,
                      int per_sample, float *out, uint64_t *stats);
@@ -1422,6 +1439,7 @@ int oracle_render_gw(const char *scene_text, int W, int H, int gw, int spp, int 
                               total.leaf_children};
             memcpy(stats, v, sizeof(v));
             stats[18] = total.cap_returns;
+            stats[19] = total.bursts, stats[20] = total.nested_bursts;
         }
         return 0;
     } catch (std::exception &e) {
@@ -1446,7 +1464,7 @@ int oracle_trace_rays(const char *scene_text, const float *rays, int n, int spp,
                                    nullptr);
 }
 
-/* the same; stats (may be null): [0] queries, [1] cap_returns */
+/* the same; stats (may be null): [0] queries, [1] cap_returns, [2] bursts, [3] nested_bursts */
 int oracle_trace_rays_stats(const char *scene_text, const float *rays, int n, int spp, int depth, uint64_t seed,
                             int sample_begin, int64_t ray_begin, int threads, int order, float *out,
                             uint64_t *stats)
@@ -1487,7 +1505,8 @@ int oracle_trace_rays_stats(const char *scene_text, const float *rays, int n, in
         if (!err.empty())
             throw std::runtime_error(err);
         if (stats)
-            stats[0] = total.queries, stats[1] = total.cap_returns;
+            stats[0] = total.queries, stats[1] = total.cap_returns, stats[2] = total.bursts,
+            stats[3] = total.nested_bursts;
         return 0;
     } catch (std::exception &e) {
         g_err = e.what();

@@ -28,7 +28,9 @@ STAT_NAMES = ["queries", "sphere_tests", "sphere_hits", "plane_tests", "merge_st
               # texture evaluations by class (oracle.cpp TexCount)
               "tex_xform", "tex_multiply", "tex_image", "tex_spherical", "tex_mirrorball", "tex_skybox", "tex_log",
               # traceRay calls the count > 1000 early return ended (include/path-trace.h:144-157)
-              "cap_returns"]
+              "cap_returns",
+              # scatter loops (sc > eps) that run; those a refraction or mirror child entered (level >= 2)
+              "bursts", "nested_bursts"]
 
 _lib = None
 
@@ -137,17 +139,21 @@ def trace_rays(scene_text: str, rays: np.ndarray, spp: int, depth: int, seed: in
                threads: int = 0, order: int = ORDER_REFERENCE, ray_begin: int = 0, stats: bool = False):
     """traceRay per caller ray (n x 7: origin, direction, strength): the mean
     of spp samples keyed (seed, ray, sample) -- pt_trace_rays' restatement.
-    With stats, also {"queries", "cap_returns"} summed over the batch."""
+    With stats, also {"queries", "cap_returns", "bursts", "nested_bursts"}
+    summed over the batch: bursts are the scatter loops (sc > eps) that run,
+    nested_bursts those a refraction or mirror child entered (recursion
+    level >= 2), not the caller's ray itself."""
     r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
     out = np.zeros((len(r), 3), dtype=np.float32)
-    st = np.zeros(2, dtype=np.uint64)
+    st = np.zeros(4, dtype=np.uint64)
     rc = lib().oracle_trace_rays_stats(scene_text.encode(), r.ctypes.data, len(r), spp, depth, seed, sample_begin,
                                        ray_begin, threads or (os.cpu_count() or 1), order, out.ctypes.data,
                                        st.ctypes.data)
     if rc != 0:
         raise RuntimeError("oracle_trace_rays: " + lib().oracle_last_error().decode())
     if stats:
-        return out, {"queries": int(st[0]), "cap_returns": int(st[1])}
+        return out, {"queries": int(st[0]), "cap_returns": int(st[1]), "bursts": int(st[2]),
+                     "nested_bursts": int(st[3])}
     return out
 
 

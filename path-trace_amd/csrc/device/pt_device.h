@@ -4699,6 +4699,13 @@ __device__ __forceinline__ int lane_walk_rs(const Env &e, RsFrame *F, int &sp, V
                 N = 1;
             const V3 rc = S::refl(mat, hit, e);
             const V3 refl = reflect(c.a, n);
+            /* PH_LOOP's i >= N at i = 0: a count that converted to INT_MIN (a NaN,
+             * infinite or huge strength) runs no child, and burst() relies on i < N */
+            if (N <= 0) {
+                r = part;
+                state = RETURN;
+                continue;
+            }
             if (Reach<S>::kr != 0 && sc > EPS) { /* a scatter loop: the wave's burst, asked for */
                 c.rc = rc, c.a = refl, c.sc = sc, c.N = N;
                 c.ms = (mat << 2) | RS_BURST;

@@ -25,10 +25,13 @@ SHEAR = Matrix(1.0, 0.5, 0.0, 0.0, 0.0, 1.0, 0.25, 0.5, 0.0, 0.0, 1.0, 0.0)
 XFORMS = (("flip", FLIP_SCALE), ("shear", SHEAR))
 
 
-def materials():
-    """the five materials of zoo.csg_zoo: diffuse, glossy, glass, mirror, emitter"""
+def materials(leaf=False):
+    """the five materials of zoo.csg_zoo: diffuse, glossy, glass, mirror, emitter.  `leaf` lowers the
+    glossy reflectance from 0.9 to 0.5 and changes nothing else: a burst's child then carries at most
+    0.5 sqrt(3) (2e-4 / 0.3) 1.01 = 5.8e-4 < eps of strength, every burst of the scene ends in leaves
+    (reach_facts["bursts_all_leaf"]) and the lane-resume form is built (tests/test_lane_resume_csg.py)."""
     diffuse = Material(ColorTexture(0.8, 0.7, 0.6), ColorTexture(1))
-    glossy = Material(ColorTexture(0.9), ColorTexture(0.3))
+    glossy = Material(ColorTexture(0.5 if leaf else 0.9), ColorTexture(0.3))
     glass = Material(ColorTexture(0.7), ColorTexture(0), ColorTexture(0), ColorTexture(0.9, 0.95, 1.0), 1.45,
                      ColorTexture(0.8))
     mirror = Material(ColorTexture(0.99), ColorTexture(0))
@@ -284,8 +287,8 @@ def assembly_centres(s):
     return [((j - (k - 1) / 2.0) * SPACING, 0.0, -8.0) for j in range(k)]
 
 
-def trace_scene(s):
-    M = materials()
+def trace_scene(s, leaf=False):
+    M = materials(leaf)
     parts = [b(c, M) for (_, b), c in zip(_assemblies(s), assembly_centres(s))]
     ground = Plane((0, 1, 0), (0, -2, 0), M[0])
     wall = Plane((0, 0, 1), (0, 0, -16), M[4])
@@ -338,6 +341,33 @@ def trace_rays(s, n=TRACE_RAYS):
     keep = (ln > 100) | (ln < 0.01) | (rng.random((len(r), 1)) < 0.3)
     r[:, 3:] = np.where(keep, r[:, 3:], r[:, 3:] / ln).astype(np.float32)
     return np.concatenate([r, strengths(rng, len(r))], axis=1).astype(np.float32)
+
+
+# the strengths a caller can pass that sit on an edge of traceRay's arithmetic: NaN and +inf (10000 x
+# strength converts to INT_MIN on x86: no scatter loop runs), a finite value past INT_MAX, a negative
+# one, eps itself (shaded: the test is strength < eps) and a value just below it (not shaded).
+# No large finite strength that leaves N positive: a refraction child scales it into bursts of 1e8 children.
+EDGE_STRENGTHS = (float("nan"), float("inf"), 1e30, -1.0, float(np.float32(1e-3)), 0.00099999)
+
+
+def edge_strength_rays(s, n=TRACE_RAYS):
+    """trace_rays(s) with the strength column cycled through EDGE_STRENGTHS"""
+    r = trace_rays(s, n)
+    r[:, 6] = np.resize(np.array(EDGE_STRENGTHS, dtype=np.float32), len(r))
+    return r
+
+
+def regress_resume_negative_count():
+    """Regression (scene, rays): a scatter loop whose count is negative.  10000 x strength x addFactor x sc
+    converts to INT_MIN where it is NaN, infinite or past INT_MAX (x86's cvttss2si), the reference's
+    `for (i = 0; i < N; i++)` runs no child and traceRay returns the emission alone (path-trace.h:128-160).
+    The lane-resume walk asked the wave for that burst without the loop's own test, and the burst, which
+    relies on i < N, ran a round of children with weights add / N.  One diffuse sphere (sc = 1) lit by an
+    emissive half-space behind the caller (z > 4); the last ray is the control (strength 1)."""
+    M = materials()
+    root = Union(Sphere((0, 0, -4), 1, M[0]), Plane((0, 0, -1), (0, 0, 4), M[4]))
+    rays = np.array([[0, 0, 0, 0, 0, -1, st] for st in EDGE_STRENGTHS[:3] + (1.0,)], dtype=np.float32)
+    return root, rays
 
 
 # --------------------------------------------------------------- cap scene ---

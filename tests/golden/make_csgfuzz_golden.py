@@ -13,6 +13,12 @@ adversarial CSG inputs of tests/csgfuzz.py, for tests/test_csgfuzz.py:
                      and takes the whole run down with it; such rays are located by
                      bisection, removed (at most 2 % of a scene's rays) and
                      the final list is run again, since a ray's engine key is its index;
+  csgfuzz_trace_leaf.npz  the same for the all-leaf variants of the trace scenes
+                     (csgfuzz.trace_scene(s, leaf=True): the scenes whose default
+                     module is the lane-resume form) and, per scene, for the
+                     edge-strength family (csgfuzz.edge_strength_rays), with
+                     the indices of the rays removed from either family, and
+                     csgfuzz.regress_resume_negative_count's rays and means;
   csgfuzz_cap.npz    rays through the cap scene: those on which that assertion
                      fires when the ray runs alone (index 0) at depth 2 -- the
                      reference's own proof that the cap is reached -- and rays it
@@ -20,7 +26,11 @@ adversarial CSG inputs of tests/csgfuzz.py, for tests/test_csgfuzz.py:
 
 Runs only where the reference tree exists.
 
-    python tests/golden/make_csgfuzz_golden.py
+    python tests/golden/make_csgfuzz_golden.py [spans] [trace] [trace_leaf]
+
+Without arguments every fixture is written; `trace` writes csgfuzz_trace.npz and
+csgfuzz_cap.npz (which holds the rays make_trace removed), `trace_leaf` only
+csgfuzz_trace_leaf.npz.
 """
 import os
 import sys
@@ -107,28 +117,56 @@ def find_abort(txt, rays, lo, hi):
     return lo
 
 
+def freeze(txt, all_rays, what):
+    """(keep, rays, mean): the reference's means of all_rays[keep], keep dropping the rays it asserts on"""
+    keep = np.ones(len(all_rays), dtype=bool)
+    while True:
+        rays = all_rays[keep]
+        mean = ref_completes(txt, rays, TRACE_DEPTH)
+        if mean is not None:
+            break
+        k = find_abort(txt, rays, 0, len(rays))
+        keep[np.flatnonzero(keep)[k]] = False
+    removed = int((~keep).sum())
+    assert removed <= MAX_REMOVED * len(all_rays), "%s: the reference asserts on %d rays" % (what, removed)
+    return keep, rays, mean
+
+
 def make_trace():
     out = {}
     moved = []
     for s in range(F.N_TRACE_SCENES):
         txt = to_text(F.trace_scene(s))
         all_rays = F.trace_rays(s)
-        keep = np.ones(len(all_rays), dtype=bool)
-        while True:
-            rays = all_rays[keep]
-            mean = ref_completes(txt, rays, TRACE_DEPTH)
-            if mean is not None:
-                break
-            k = find_abort(txt, rays, 0, len(rays))
-            keep[np.flatnonzero(keep)[k]] = False
+        keep, rays, mean = freeze(txt, all_rays, "scene %d" % s)
         removed = int((~keep).sum())
-        assert removed <= MAX_REMOVED * len(all_rays), "scene %d: the reference asserts on %d rays" % (s, removed)
         moved.append((np.flatnonzero(~keep).astype(np.int32), all_rays[~keep]))
         out["text_%d" % s], out["rays_%d" % s], out["mean_%d" % s] = np.array(txt), rays, mean
         print("trace scene %d: %d rays, %d removed, mean %s" % (s, len(rays), removed, mean.mean(axis=0)))
     np.savez_compressed(os.path.join(HERE, "csgfuzz_trace.npz"),
                         meta=np.array([TRACE_SPP, TRACE_DEPTH, SEED], dtype=np.int64), **out)
     return moved
+
+
+def make_trace_leaf():
+    """csgfuzz_trace_leaf.npz; touches no other fixture"""
+    out = {}
+    for s in range(F.N_TRACE_SCENES):
+        txt = to_text(F.trace_scene(s, leaf=True))
+        out["text_%d" % s] = np.array(txt)
+        for tag, all_rays in (("", F.trace_rays(s)), ("edge_", F.edge_strength_rays(s))):
+            keep, rays, mean = freeze(txt, all_rays, "leaf scene %d %srays" % (s, tag))
+            assert not np.isnan(mean).any(), (s, tag)
+            out["%srays_%d" % (tag, s)], out["%smean_%d" % (tag, s)] = rays, mean
+            out["%smoved_index_%d" % (tag, s)] = np.flatnonzero(~keep).astype(np.int32)
+            print("leaf trace scene %d %srays: %d rays, %d removed, mean %s" % (s, tag, len(rays), int((~keep).sum()),
+                                                                              mean.mean(axis=0)))
+    root, rays = F.regress_resume_negative_count()
+    out["regress_text"], out["regress_rays"] = np.array(to_text(root)), rays
+    out["regress_mean"] = O.ref_trace_rays(to_text(root), rays, TRACE_SPP, TRACE_DEPTH, seed=SEED)
+    print("regress_resume_negative_count: %s" % out["regress_mean"])
+    np.savez_compressed(os.path.join(HERE, "csgfuzz_trace_leaf.npz"),
+                        meta=np.array([TRACE_SPP, TRACE_DEPTH, SEED], dtype=np.int64), **out)
 
 
 def make_cap(moved):
@@ -155,8 +193,14 @@ def make_cap(moved):
 def main():
     if not O.ref_available():
         sys.exit("needs `make -C oracle ref` (the reference tree)")
-    make_spans()
-    make_cap(make_trace())
+    what = sys.argv[1:] or ["spans", "trace", "trace_leaf"]
+    assert set(what) <= {"spans", "trace", "trace_leaf"}, what
+    if "spans" in what:
+        make_spans()
+    if "trace" in what:
+        make_cap(make_trace())
+    if "trace_leaf" in what:
+        make_trace_leaf()
 
 
 if __name__ == "__main__":

@@ -8,6 +8,13 @@ form off also the burst counters the oracle has no counterpart of (`leaf`
 counts burst children only, `dark` and the pass counters are the kernel's
 own), which must not move because the bursts are the same bursts.
 
+The scenes here are scene_p1, a forcing scene and one sheared sphere: two
+Difference nodes, no Intersection, one transform, no span tie.  The
+adversarial CSG of tests/csgfuzz.py (ties, Intersections, transforms over
+Differences), the strengths on the edges of traceRay's arithmetic, the census
+of suspended lanes and full chunks over that geometry are in
+tests/test_lane_resume_csg.py, which shares COUNTERS and ORDERS.
+
 The modules are listed in tests/precompile_lane_resume.py.
 """
 import os
