@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <fstream>
 #include <sstream>
 #include <vector>
 
@@ -522,16 +521,7 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     const char *jit_opts = getenv("PT_JIT_OPTIONS");
     const bool maxocc = root.find("Diff<") != std::string::npos && s.lane_walk == 0 && !s.lane_scatter &&
                         !(jit_opts && strstr(jit_opts, "sched-strategy"));
-    /* experiment hook: A/B a different device library text in the same run,
-     * e.g. PT_DEVICE_HEADER=tools/ab/old.h (profiling only) */
-    if (const char *hdr = getenv("PT_DEVICE_HEADER")) {
-        std::ifstream f(hdr);
-        if (!f)
-            throw Error(PT_ERR_ARG, std::string("PT_DEVICE_HEADER not readable: ") + hdr);
-        src << f.rdbuf() << "\n";
-    } else {
-        src << device_library_source() << "\n";
-    }
+    src << device_library_source() << "\n";
     if (!g.user_obj.empty())
         src << device_user_object_source() << "\n";
     if (g.multi_span)

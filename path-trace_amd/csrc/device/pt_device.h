@@ -40,6 +40,18 @@
 #ifndef PT_DEVICE_H
 #define PT_DEVICE_H
 
+/* Retired build-time knobs: their A/B records (profiles/) still quote them, so
+ * an old command line must fail here instead of timing the default as a variant. */
+#if defined(PT_KEPT_NORM) || defined(PT_FAST_NORM) || defined(PT_FAST_MIRRORBALL) || defined(PT_UNIT_RAY) ||        \
+    defined(PT_INERT) || defined(PT_PLANE_AXIS_DARK) || defined(PT_PLANE_AXIS_DIV) || defined(PT_MERGE_FROM_SPANS) || \
+    defined(PT_UNION_FUSED) || defined(PT_CTX_VGPR) || defined(PT_CLEAR_UNION) || defined(PT_LSUM_LDS) ||             \
+    defined(PT_RING_SPLIT) || defined(PT_LANE_MAJOR) || defined(PT_LM_CHAINS) || defined(PT_LM_BITS) ||               \
+    defined(PT_RING_FITS) || defined(PT_PASS_PAIR_FALLBACK) || defined(PT_KATT_SHORT) || defined(PT_SHORT_REM) ||     \
+    defined(PT_PAD_VALU) || defined(PT_PAD_SALU) || defined(PT_NO_AXIS_SHARE) || defined(PT_FAST_LANE) ||             \
+    defined(PT_RECEDE_DEAD)
+#error "a retired build-time knob is defined (PT_KEPT_NORM PT_FAST_NORM PT_FAST_MIRRORBALL PT_UNIT_RAY PT_INERT PT_PLANE_AXIS_DARK PT_PLANE_AXIS_DIV PT_MERGE_FROM_SPANS PT_UNION_FUSED PT_CTX_VGPR PT_CLEAR_UNION PT_LSUM_LDS PT_RING_SPLIT PT_LANE_MAJOR PT_LM_CHAINS PT_LM_BITS PT_RING_FITS PT_PASS_PAIR_FALLBACK PT_KATT_SHORT PT_SHORT_REM PT_PAD_VALU PT_PAD_SALU PT_NO_AXIS_SHARE PT_FAST_LANE PT_RECEDE_DEAD): its arm is gone, see DESIGN.md s2, Build-time knobs that remain"
+#endif
+
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
@@ -241,34 +253,17 @@ __device__ __forceinline__ V3 cnormalize(V3 v) /* == normalize(v), bitwise */
  * and 1e-3 < |w| < 1.01 (den_ok, and m != 0); each component is a u11 value,
  * +0 or of magnitude in [2^-24, 1] (num_ok, or a +0 numerator, whose quotient
  * div_core also gets exactly: +0).  Same bits as normalize(). */
-#ifndef PT_KEPT_NORM
-#define PT_KEPT_NORM 1
-#endif
 __device__ __forceinline__ V3 cnormalize_kept(V3 v)
 {
-#if PT_KEPT_NORM
     const Rcp R = mkrcp(sqrt_core(dot(v, v)));
     return mk(div_core(v.x, R), div_core(v.y, R), div_core(v.z, R));
-#else
-    return cnormalize(v);
-#endif
 }
-/* normalize() where the device library needs it (normals, reflect / refract,
- * the spherical sky map): PT_FAST_NORM=1 takes the exact fast sequence (same
- * bits).  Off: same-box A/B (profiles/round5/ab_grab_fastnorm_c3_full.txt)
- * C5 -3.6 % (its lane walks carry the extra branches), C3 -0.8 %, C2 +1.2 %
- * -- the mirror-ball map's part, which PT_FAST_MIRRORBALL keeps */
-#ifndef PT_FAST_NORM
-#define PT_FAST_NORM 0
-#endif
-#ifndef PT_FAST_MIRRORBALL /* off: same-box C2 A/B -2.4 % .. +1.2 % (noise), profiles/round5/ab_grab_adaptive.txt */
-#define PT_FAST_MIRRORBALL 0
-#endif
-#if PT_FAST_NORM
-#define PT_NORM(v) cnormalize(v)
-#else
-#define PT_NORM(v) normalize(v)
-#endif
+/* Where the device library itself normalises (normals, reflect / refract,
+ * the sky maps) it calls the plain normalize(): cnormalize's exact fast
+ * sequence there measured C5 -3.6 % (its lane walks carry the extra branches),
+ * C3 -0.8 %, C2 +1.2 % (same-box A/B, profiles/round5/ab_grab_fastnorm_c3_full.txt),
+ * and in the mirror-ball map alone C2 -2.4 % .. +1.2 %, noise
+ * (profiles/round5/ab_grab_adaptive.txt) */
 /* (int)x as x86 cvttss2si: out-of-range and NaN give INT_MIN (the reference
  * runs on x86; v_cvt_i32_f32 would saturate / give 0). */
 __device__ __forceinline__ int cvt_x86(float x)
@@ -283,7 +278,7 @@ __device__ __forceinline__ float clamp01(float x)
 /* Vector3D::reflect, vector3d.h:186-190 */
 __device__ __forceinline__ V3 reflect(V3 d, V3 n)
 {
-    n = PT_NORM(n);
+    n = normalize(n);
     return d - (2.0f * dot(d, n)) * n;
 }
 __device__ __forceinline__ bool bad_ior(float ior, V3 n, V3 d)
@@ -296,8 +291,8 @@ __device__ __forceinline__ float refract_strength(V3 d, float ior, V3 n)
 {
     if (bad_ior(ior, n, d))
         return 0.0f;
-    n = PT_NORM(n);
-    V3 inc = PT_NORM(d);
+    n = normalize(n);
+    V3 inc = normalize(d);
     float c = dot(inc, n);
     float r = 1.0f - ior * ior * (1.0f - c * c);
     if (r <= 0.0f)
@@ -309,17 +304,13 @@ __device__ __forceinline__ V3 refract(V3 d, float ior, V3 n)
 {
     if (bad_ior(ior, n, d))
         return mk(0, 0, 0);
-    n = PT_NORM(n);
-    V3 inc = PT_NORM(d);
+    n = normalize(n);
+    V3 inc = normalize(d);
     float c = dot(inc, n);
     float arg = 1.0f - ior * ior * (1.0f - c * c);
     if (arg < 0.0f)
         return mk(0, 0, 0);
-#if PT_FAST_NORM
-    return PT_NORM(ior * inc - (ior * c + csqrt(arg)) * n);
-#else
-    return PT_NORM(ior * inc - (ior * c + __builtin_sqrtf(arg)) * n);
-#endif
+    return normalize(ior * inc - (ior * c + __builtin_sqrtf(arg)) * n);
 }
 /* Matrix::apply / applyNoTranslate, transform.h:408-421; m in ctor order */
 __device__ __forceinline__ V3 m_apply(const float *__restrict__ m, V3 v)
@@ -401,21 +392,6 @@ __device__ __forceinline__ int mask_sel(u64 m, int a, int b)
 {
     int r;
     asm("v_cndmask_b32_e64 %0, %2, %1, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
-    return r;
-}
-/* v + this lane's bit of the uniform mask m: one v_addc with m as carry-in */
-__device__ __forceinline__ int add_lane_bit(int v, u64 m)
-{
-    int r;
-    u64 co;
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r), "=s"(co) : "v"(v), "s"(m));
-    return r;
-}
-/* 0 where this lane's bit of the uniform mask m is set, else v */
-__device__ __forceinline__ int zero_if(u64 m, int v)
-{
-    int r;
-    asm("v_cndmask_b32_e64 %0, %1, 0, %2" : "=v"(r) : "v"(v), "s"(m));
     return r;
 }
 /* base + set bits of the uniform mask m in the lanes below this one (v_mbcnt) */
@@ -572,9 +548,6 @@ __device__ __forceinline__ void start_from_start(CS &a, const CS &b) { a.t0 = b.
 
 /* One query direction as every primitive of a traversal sees it: |d|^2 and
  * its refined reciprocal are shared (the sphere quotients all divide by a). */
-#ifdef PT_NO_AXIS_SHARE /* A/B hook: every plane takes its own reciprocal */
-#undef PT_AXIS_SHARE
-#endif
 struct Ray
 {
     V3 d;
@@ -608,15 +581,10 @@ __device__ __forceinline__ Ray mkray(V3 d)
 }
 /* The same for a normalised direction (the burst passes' children): |d|^2 is
  * 1 within 1e-6, so den_ok(a) holds and the spans' quotient checks fold */
-#ifndef PT_UNIT_RAY
-#define PT_UNIT_RAY 1
-#endif
 __device__ __forceinline__ Ray mkray_unit(V3 d)
 {
     Ray q = mkray(d);
-#if PT_UNIT_RAY
     q.aok = 1;
-#endif
     return q;
 }
 
@@ -675,13 +643,10 @@ __device__ __forceinline__ int sep(const PS &ps, int x, int y)
  * Only positives: a B-side span that ends before EPS can still trigger the
  * quirk on the A span it overlaps. */
 enum { NODE_ISECT = 0, NODE_UNION = 1, NODE_DIFF = 2 };
-#ifndef PT_INERT
-#define PT_INERT 1
-#endif
 template <class PS>
 __device__ __forceinline__ int inert(const PS &ps, int x)
 {
-    return PT_INERT ? ps.live[x] & (ps.t1[x] < EPS) : 0;
+    return ps.live[x] & (ps.t1[x] < EPS);
 }
 template <int KIND, class PS>
 __device__ __forceinline__ int pair_ok(const PS &ps, int x, int y)
@@ -755,21 +720,9 @@ struct Sph
     {
         const float b = dot(c.omc, q.d);
         const float disc = b * b - q.a * c.c;
-#if PT_RECEDE_DEAD
-        /* Experiment hook, off: exact, but C2 -4 % (the waves whose only live
-         * lanes recede are rare; profiles/round6/ab_recede_dead_c2_not_kept.txt).
-         * Union-only trees: a sphere the ray leaves from outside
-         * (c > 0, b >= 0) has t1 <= 0 -- fl(a*c) >= 0 makes disc <= fl(b*b),
-         * so sqrt(disc) <= b -- and a span ending before EPS changes no union
-         * result: the union rule never takes it, and in the lazy merge it can
-         * only join spans that start before EPS, whose ends (and end normals)
-         * it never supplies (src/union.cpp:84-134, path-trace.h:66-100).  Such
-         * a lane counts as dead, so a wave whose other lanes miss skips the
-         * root and the divisions. */
-        const bool live = !(disc <= EPS) && !(c.c > 0.0f && b >= 0.0f);
-#else
+        /* (counting a sphere the ray leaves from outside as dead too is exact
+         * in union-only trees, but C2 -4 %: profiles/round6/ab_recede_dead_c2_not_kept.txt) */
         const bool live = !(disc <= EPS);
-#endif
 #if PT_SPHERE_SKIP
         /* no lane meets the sphere: skip the root and the divisions (a dead
          * span's bounds are never read) */
@@ -846,7 +799,7 @@ struct Sph
     __device__ static __forceinline__ int fast_ok(const PS &) { return 1; }
     __device__ static __forceinline__ V3 normal(int, float t, V3 o, V3 d, const Env &e)
     {
-        return PT_NORM((o + t * d) - mk(e.P[OFF], e.P[OFF + 1], e.P[OFF + 2]));
+        return normalize((o + t * d) - mk(e.P[OFF], e.P[OFF + 1], e.P[OFF + 2]));
     }
     /* Sound test on an UNNORMALISED direction w that the span of normalize(w)
      * is dead or ends before EPS (the generation round's dark test).  Origin
@@ -884,12 +837,6 @@ struct Sph
 };
 
 /* Plane half-space {p : n.p + d < 0} (src/plane.cpp:35-63).  P[OFF..] = n, d. */
-#ifndef PT_PLANE_AXIS_DARK
-#define PT_PLANE_AXIS_DARK 1
-#endif
-#ifndef PT_PLANE_AXIS_DIV
-#define PT_PLANE_AXIS_DIV 1 /* an axis-aligned plane's d.n as one product */
-#endif
 /* AX >= 0: the normal has one nonzero component, axis AX >> 1, negative if
  * AX & 1 (codegen knows the scene's numbers); -1 otherwise. */
 /* UNIT: the normal is +-e_(AX >> 1) exactly and the scene has another such
@@ -924,7 +871,7 @@ struct Pln
     __device__ static __forceinline__ void init(St &s, const Ctx &c, const Ray &q, const Env &e)
     {
         float div;
-        if constexpr (AX >= 0 && PT_PLANE_AXIS_DIV) {
+        if constexpr (AX >= 0) {
             /* one nonzero component: (d.x n.x + d.y n.y) + d.z n.z is that
              * component's product plus signed zeros -- the product itself
              * whenever it is nonzero, and a zero either way when it is zero
@@ -1014,7 +961,7 @@ struct Pln
     __device__ static __forceinline__ int fast_ok(const PS &) { return 1; }
     __device__ static __forceinline__ V3 normal(int, float, V3, V3, const Env &e)
     {
-        return PT_NORM(mk(e.P[OFF], e.P[OFF + 1], e.P[OFF + 2]));
+        return normalize(mk(e.P[OFF], e.P[OFF + 1], e.P[OFF + 2]));
     }
     /* Sound dark test on an unnormalised direction w (see Sph::dark_mask).
      * With num <= -1e-6 the span of normalize(w) is dead or ends before EPS
@@ -1040,7 +987,7 @@ struct Pln
         if constexpr (!SEL::take(MAT))
             return ~0ull;
         const V3 np = mk(e.P[OFF], e.P[OFF + 1], e.P[OFF + 2]);
-        if constexpr (AX >= 0 && PT_PLANE_AXIS_DARK) {
+        if constexpr (AX >= 0) {
             /* the exact n.w is n_a * w_a: its sign test is one compare (the
              * bound above holds for an exact n.w >= 0 as for a computed one) */
             const float wa = (AX >> 1) == 0 ? w.x : (AX >> 1) == 1 ? w.y : w.z;
@@ -1761,10 +1708,10 @@ struct Xf
         if constexpr (!C::NO_DIFF) {
             const bool neg = BFlips<C>::of(prim) & 1;
             n = neg ? -n : n;
-            n = PT_NORM(m_lin(e.P + IOFF, n));
+            n = normalize(m_lin(e.P + IOFF, n));
             return neg ? -n : n;
         }
-        return PT_NORM(m_lin(e.P + IOFF, n));
+        return normalize(m_lin(e.P + IOFF, n));
     }
     /* no raw-direction dark test through a transform unless nothing inside is selected */
     template <class SEL>
@@ -1883,9 +1830,6 @@ __device__ __forceinline__ int span_first_hit(const PS &ps, bool &hit, float &t,
 }
 
 /* Spine and lane queries start the lazy merge from the spans they computed */
-#ifndef PT_MERGE_FROM_SPANS
-#define PT_MERGE_FROM_SPANS 1
-#endif
 /* The spine's query (one ray, the same on every lane): span_first_hit where
  * the checks hold, else the lazy merge.  The checks are wave-uniform here. */
 template <class R>
@@ -1900,12 +1844,8 @@ __device__ __forceinline__ bool spine_first_hit(const typename R::Ctx &ctx, V3 d
     if (!wave_any(!fok))
         return hit;
     merged = 1;
-#if PT_MERGE_FROM_SPANS
     (void)ctx, (void)d, (void)e;
     return first_hit_ps<R>(ps, t, ref, exit_hit);
-#else
-    return first_hit<R>(ctx, d, e, t, ref, exit_hit);
-#endif
 }
 
 #ifdef PT_BAIL_STATS /* diagnostic builds: which chunks a merge-free kernel could finish */
@@ -1918,7 +1858,7 @@ template <class R>
 __device__ __forceinline__ bool lane_first_hit(const typename R::Ctx &ctx, V3 d, const Env &e, float &t, u32 &ref,
                                                bool &exit_hit)
 {
-#if defined(PT_FAST_SPINE) || defined(PT_FAST_LANE)
+#ifdef PT_FAST_SPINE
     PrimSpans<R::HI> ps;
     R::span(ps, ctx, mkray(d), e);
     bool hit;
@@ -1929,11 +1869,7 @@ __device__ __forceinline__ bool lane_first_hit(const typename R::Ctx &ctx, V3 d,
             pt_bail_mark();
 #endif
         if (!fok)
-#if PT_MERGE_FROM_SPANS
             hit = first_hit_ps<R>(ps, t, ref, exit_hit);
-#else
-            hit = first_hit<R>(ctx, d, e, t, ref, exit_hit);
-#endif
     }
     return hit;
 #else
@@ -2033,9 +1969,6 @@ __device__ __forceinline__ int cheap_ok(const PS &ps)
  * is that primitive's entry at b0 unless b0 >= MAXV -- fast_first_hit's exit
  * branch (b0 < EPS) cannot occur.  Returns the rule's verdict; hit / t / mat
  * are valid where it holds. */
-#ifndef PT_UNION_FUSED
-#define PT_UNION_FUSED 1
-#endif
 template <class R, class PS>
 __device__ __forceinline__ int union_first_hit(const PS &ps, bool &hit, float &t, int &mat)
 {
@@ -2372,26 +2305,13 @@ __device__ __forceinline__ V3 mirrorball_map(V3 v) /* transform_texture.h:46-59 
 {
     if (is_zero(v))
         return mk(0, 0, 0);
-#if PT_FAST_MIRRORBALL /* cnormalize / csqrt / cdiv: the same bits as normalize, sqrtf and '/' */
-    v = cnormalize(v);
-#else
-    v = PT_NORM(v);
-#endif
+    v = normalize(v);
     if (v.z <= -1.0f)
         return mk(0, 0.5f, 0);
-#if PT_FAST_MIRRORBALL
-    float d = csqrt(2.0f + 2.0f * v.z);
-    if (d == 0.0f)
-        return mk(0, 0.5f, 0);
-    const Rcp rd = mkrcp(d);
-    const bool dok = den_ok(d);
-    float xt = cdiv(v.x, rd, dok), yt = cdiv(v.y, rd, dok);
-#else
     float d = __builtin_sqrtf(2.0f + 2.0f * v.z);
     if (d == 0.0f)
         return mk(0, 0.5f, 0);
     float xt = v.x / d, yt = v.y / d;
-#endif
     return mk((float)((double)xt * 0.5 + 0.5), (float)((double)yt * 0.5 + 0.5), 0);
 }
 /* The reference's std::atan2(float, float) and std::asin(float) are glibc's
@@ -2519,7 +2439,7 @@ __device__ __forceinline__ V3 spherical_map(V3 v) /* transform_texture.h:73-85 *
     const double PI = 3.14159265358979323846;
     if (is_zero(v))
         return mk(0, 0, 0);
-    v = PT_NORM(v);
+    v = normalize(v);
     float theta = libm_atan2f(v.y, v.x);
     if ((double)theta < -PI)
         theta = (float)((double)theta + 2 * PI);
@@ -2623,25 +2543,6 @@ __device__ __forceinline__ T lds_get(const LdsBox<T> &b)
         u.w[i] = b.w[i];
     return u.t;
 }
-/* the same, each word kept a vector value (an empty asm on it): the
- * compiler cannot turn the uniform words into SGPRs, which a scene under
- * SGPR pressure spills into VGPR lanes and reads back one v_readlane at a time */
-template <class T>
-__device__ __forceinline__ T lds_get_v(const LdsBox<T> &b)
-{
-    union
-    {
-        float4 w[LdsBox<T>::N];
-        T t;
-    } u;
-#pragma unroll
-    for (int i = 0; i < LdsBox<T>::N; i++) {
-        float4 v = b.w[i];
-        asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-        u.w[i] = v;
-    }
-    return u.t;
-}
 template <class T>
 __device__ __forceinline__ void lds_put(LdsBox<T> &b, const T &t)
 {
@@ -2662,51 +2563,13 @@ __device__ __forceinline__ void lds_put(LdsBox<T> &b, const T &t)
 #ifndef PT_SCALAR_WAVE
 #define PT_SCALAR_WAVE -1
 #endif
-/* the pass queries' primitive contexts as vector values (lds_get_v); same-box
- * A/B (profiles/round4/ab_ctx_vgpr.txt): C3 -0.8 %, C2 and C5 +-1 % -- off */
-#ifndef PT_CTX_VGPR
-#define PT_CTX_VGPR 0
-#endif
-/* the clear pass in union-only scenes too (round 2: off, C2 2.94 -> 3.37) */
-#ifndef PT_CLEAR_UNION
-#define PT_CLEAR_UNION 0
-#endif
-/* lane-major ring entries as two stores (C2 +8 %, C3 and C5 +-0, same A/B) */
 /* lane index recomputed at each use in bursts (lane_id) or held in a
  * register; -1 = by scene: same-box A/B (profiles/round4/ab_lane_remat_lsum_lds.txt)
  * Difference-free trees (C2) +6 %, C3 -1 %, C5 -0.1 % */
 #ifndef PT_LANE_REMAT
 #define PT_LANE_REMAT -1
 #endif
-/* the fast order's lane sums in LDS instead of registers: -1 = where the
- * 768 B per wave leave the workgroups per CU unchanged (min_workgroups).
- * Off: C2 +1..2.5 % alone, nothing on top of PT_LANE_REMAT; C3, C5 +-0 */
-#ifndef PT_LSUM_LDS
-#define PT_LSUM_LDS 0
-#endif
-#ifndef PT_RING_SPLIT
-#define PT_RING_SPLIT 1
-#endif
-#ifndef PT_LANE_MAJOR
-#define PT_LANE_MAJOR 1 /* deferred rounds: lane l evaluates attempts 8l..8l+7 (one chained stream) */
-#endif
-#ifndef PT_LM_CHAINS
-#define PT_LM_CHAINS 1 /* lane-major rounds: engine chains per lane (2: the halves interleaved) */
-#endif
-#ifndef PT_LM_BITS
-#define PT_LM_BITS 1 /* lane-major rounds: per-lane bit planes + one wave prefix sum (burst_t) */
-#endif
-#ifndef PT_RING_FITS
-#define PT_RING_FITS 1 /* PT_LM_BITS: the ring writes of a round whose kept attempts all fit skip the slot test */
-#endif
 
-#ifndef PT_PASS_PAIR_FALLBACK
-/* 0: in a burst's fast pass over a Difference-free tree, lanes the one-pass
- * check cannot decide go to the full merge directly instead of through the
- * pairwise checks (whose all-pairs code raises the pass's register pressure
- * for lanes that are rare there) */
-#define PT_PASS_PAIR_FALLBACK 0
-#endif
 /* Per-wave LDS work areas of the scatter loop. */
 struct WaveLds
 {
@@ -2745,15 +2608,6 @@ enum { B_DONE = 0, B_ABORT = 1, B_NONLEAF = 2 };
 #ifndef PT_KATT
 #define PT_KATT 8 /* rejection attempts per lane per generation round (A/B on C3: 4 -> 8 +6%) */
 #endif
-#ifndef PT_KATT_SHORT
-/* per lane, in a short round; off (= PT_KATT) by default: short rounds of 2
- * cost C3 6 % (same-box A/B 143.4 vs 152.0 Msamples/s at 256 spp), and the
- * bursts they were for (matBrightDiffuseWhite's) are walked by lanes */
-#define PT_KATT_SHORT PT_KATT
-#endif
-#ifndef PT_SHORT_REM
-#define PT_SHORT_REM 24 /* children left at or below which a round is short (~91 attempts) */
-#endif
 #define PT_RCAP 256  /* kept-child slots per wave awaiting their lane-sum accumulation */
 #define PT_SCAP 128  /* mid / slow queue entries (< 128 pending by construction; byte ring numbers) */
 static_assert(PT_KATT % 2 == 0, "deferred rounds evaluate attempts in pairs");
@@ -2761,7 +2615,7 @@ static_assert(PT_KATT % 2 == 0, "deferred rounds evaluate attempts in pairs");
 static_assert(64 * PT_KATT < PT_JUMP_ENTRIES, "jump table too short for PT_KATT");
 /* lane-major rounds count a lane's trailing failures in 4 balloted bit planes */
 static_assert(PT_KATT <= 15, "a lane's trailing-failure count must fit 4 bits");
-/* PT_LM_BITS: a round's totals in 10-bit fields of one packed wave prefix sum */
+/* ... and a round's totals in 10-bit fields of one packed wave prefix sum */
 static_assert(64 * PT_KATT < 1024, "round totals must fit 10 bits");
 
 /* One rejection attempt of the scatter loop body (path-trace.h:141-158):
@@ -2792,22 +2646,6 @@ __device__ __forceinline__ Attempt attempt(u64 s0, V3 n, V3 kR, float sc, float 
     Attempt a;
     /* one ballot per compare (a ballot of a combined predicate is lowered
      * through a v_cndmask / v_cmp round trip) */
-#ifdef PT_PAD_VALU /* experiment: extra independent VALU work per attempt */
-    {
-        float pad = v.x;
-        for (int i = 0; i < PT_PAD_VALU; i++)
-            asm volatile("v_add_f32 %0, %0, %0" : "+v"(pad));
-        asm volatile("" ::"v"(pad));
-    }
-#endif
-#ifdef PT_PAD_SALU /* experiment: extra SALU work per attempt */
-    {
-        int pad = 0;
-        for (int i = 0; i < PT_PAD_SALU; i++)
-            asm volatile("s_add_u32 %0, %0, 1" : "+s"(pad));
-        asm volatile("" ::"s"(pad));
-    }
-#endif
     const u64 BB = __ballot(ball), HB = __ballot(hemi);
     a.A = BB & HB;
     a.F = BB & ~HB;
@@ -2824,8 +2662,8 @@ __device__ __forceinline__ Attempt attempt(u64 s0, V3 n, V3 kR, float sc, float 
     return a;
 }
 
-/* Two attempts of a deferred burst (attempts k and k + 1 of a lane: engine
- * states s0a, s0b) in packed f32 (v_pk_fma / v_pk_mul / v_pk_add, one
+/* Two attempts of a deferred burst (attempts k and k + 1 of a lane: draws
+ * a1..a3, b1..b3) in packed f32 (v_pk_fma / v_pk_mul / v_pk_add, one
  * instruction for both): element-wise the same IEEE operations in the same
  * order as attempt<true, KR0>, so the same bits. */
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -2837,13 +2675,6 @@ struct Attempt2
 };
 template <bool KR0>
 __device__ __forceinline__ Attempt2 attempt2_draws(W2 a1, W2 a2, W2 a3, W2 b1, W2 b2, W2 b3, V3 n, V3 kR);
-template <bool KR0>
-__device__ __forceinline__ Attempt2 attempt2(u64 s0a, u64 s0b, V3 n, V3 kR)
-{
-    const W2 a1 = lcg_step({(u32)s0a, (u32)(s0a >> 32)}), a2 = lcg_step(a1), a3 = lcg_step(a2);
-    const W2 b1 = lcg_step({(u32)s0b, (u32)(s0b >> 32)}), b2 = lcg_step(b1), b3 = lcg_step(b2);
-    return attempt2_draws<KR0>(a1, a2, a3, b1, b2, b3, n, kR);
-}
 /* Two CONSECUTIVE attempts of one lane's stream (lane-major rounds): the
  * second starts where the first's three draws end; s advances past both. */
 template <bool KR0>
@@ -2852,18 +2683,6 @@ __device__ __forceinline__ Attempt2 attempt2_chain(u64 &s, V3 n, V3 kR)
     const W2 a1 = lcg_step({(u32)s, (u32)(s >> 32)}), a2 = lcg_step(a1), a3 = lcg_step(a2);
     const W2 b1 = lcg_step(a3), b2 = lcg_step(b1), b3 = lcg_step(b2);
     s = ((u64)b3.hi << 32) | (u64)b3.lo;
-    return attempt2_draws<KR0>(a1, a2, a3, b1, b2, b3, n, kR);
-}
-/* Two attempts from two independent streams (sa, sb), each advanced past its
- * attempt's three draws: the two engine chains interleave. */
-template <bool KR0>
-__device__ __forceinline__ Attempt2 attempt2_split(u64 &sa, u64 &sb, V3 n, V3 kR)
-{
-    const W2 a1 = lcg_step({(u32)sa, (u32)(sa >> 32)}), b1 = lcg_step({(u32)sb, (u32)(sb >> 32)});
-    const W2 a2 = lcg_step(a1), b2 = lcg_step(b1);
-    const W2 a3 = lcg_step(a2), b3 = lcg_step(b2);
-    sa = ((u64)a3.hi << 32) | (u64)a3.lo;
-    sb = ((u64)b3.hi << 32) | (u64)b3.lo;
     return attempt2_draws<KR0>(a1, a2, a3, b1, b2, b3, n, kR);
 }
 template <bool KR0>
@@ -3006,8 +2825,6 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
         jread(J.j3, lane, jA, jG);
         return jA * rng.st + jG;
     };
-    /* lane-major rounds (deferred bursts): lane l's first attempt is 8l */
-    constexpr bool LMAJ = DEFERRED && PT_LANE_MAJOR && PT_KATT_SHORT == PT_KATT;
     const u64 A64 = jump[128], g64inc = jump[129] * LCG_INC;   /* 64 attempts = 192 draws  */
     const u64 Afull = jump[128 * PT_KATT], gfullinc = jump[128 * PT_KATT + 1] * LCG_INC; /* a full round */
     int fails = 0, reason = -1;
@@ -3042,7 +2859,7 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
     /* union-only scenes skip it: their first pass takes every primitive's
      * span and the union rule at once, which decides nearly every lane and
      * saves the mid queue's second pass (C2 2.94 -> 3.37 Msamples/s) */
-    constexpr bool CLEAR = S::Root::template clear_ok<Emissive<S>>() && (PT_CLEAR_UNION || !S::Root::UNION_ONLY);
+    constexpr bool CLEAR = S::Root::template clear_ok<Emissive<S>>() && !S::Root::UNION_ONLY;
     /* RAW: dark children are decided on the unnormalised direction (dark_mask,
      * sound but conservative).  The zero term also needs a factor >= +0, i.e.
      * a computed dot(normalize(w), n) >= 0: accepted w have a computed
@@ -3077,8 +2894,7 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
             d |= Occl<typename S::Root>::template occ<Emissive<S>>(c0, wn, occ_g, e);
         return d & raw_mask;
     };
-    /* children recurse for factor >= eps / (sNa |rc|): short rounds when that
-     * is below 0.99 (over 1 % of the children recurse) */
+    /* children recurse for factor >= eps / (sNa |rc|) */
     const bool short_nd = !DEFERRED && EPS < 0.99f * (sNa * abs_rc);
     /* queued slots hold ring numbers mod 256; every pending one lies in
      * [keep_sum, keep_sum + PT_RCAP), which restores it */
@@ -3101,16 +2917,19 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
              * slots are not written (they could overwrite pending ones), and a
              * round consumes no kept child without a slot.  So the masks die
              * right after their writes, and only the rare round that stops
-             * early needs them again: it evaluates the attempts a second time. */
+             * early needs them again: it evaluates the attempts a second time.
+             * Every round is a full one: short rounds of 2 attempts per lane for
+             * bursts with few children left cost C3 6 % (same-box A/B 143.4 vs
+             * 152.0 Msamples/s at 256 spp, round 3), and the bursts whose children
+             * often recurse (matBrightDiffuseWhite's) are walked by lanes.
+             * Lane-major rounds (below) with two engine chains per lane: bit-exact,
+             * -0.8 %. */
             int rem = N - (i + npos);
-            /* Short rounds (64 * PT_KATT_SHORT attempts) where a full round
-             * would mostly be thrown away: a burst with few children left (a
-             * recursing child's own small burst), or one whose children often
-             * recurse -- a non-leaf child ends the round, and with factor =
-             * 1 - (1 - cos) sc the child strength (sNa factor) |rc| reaches
-             * eps for factor >= eps / (sNa |rc|) (matBrightDiffuseWhite's
-             * bursts: a quarter of its children) */
-            const int katt = (rem <= PT_SHORT_REM || (!DEFERRED && short_nd)) ? PT_KATT_SHORT : PT_KATT;
+            /* (both arms are PT_KATT since the short rounds went; katt, short_nd and
+             * the tests on them stay until a measured change goes through here:
+             * folding them by hand reorders instructions in most modules and
+             * changes register allocation in some, profiles/round9/same_code_knob_fold.txt) */
+            const int katt = (rem <= 24 || (!DEFERRED && short_nd)) ? PT_KATT : PT_KATT;
             int free_slots = PT_RCAP - (nkeep - keep_sum);
 #ifdef PT_ROOM_CAP
             free_slots = min(free_slots, PT_ROOM_CAP); /* test hook: force early round ends */
@@ -3118,26 +2937,22 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
             int ta = 0, tk = 0; /* accepted / kept attempts of the round */
             u64 nlor = 0ull, Alast = 0ull, Flast = 0ull;
             /* One attempt's ring entry (kept, with a free slot).  A deferred
-             * burst parks the attempt's engine state (8 bytes, one register
+             * burst parks the lane's engine state instead (8 bytes, one register
              * pair): the first pass draws its three numbers again, which costs
              * less there -- 64 kept children per wave instruction -- than
              * moving the direction into a 16-byte store here, where a wave
              * instruction covers 64 attempts of which few are kept.  The
              * store runs under exec = kept mask & slot available. */
             const int slot_end = nkeep + free_slots;
-            auto write_attempt = [&](u64 A, u64 kp, u64 st, V3 wn, float factor) {
+            auto write_attempt = [&](u64 A, u64 kp, V3 wn, float factor) {
                 const int slot = mbcnt(kp, nkeep + tk);
-                if (in_mask(kp & __ballot(slot < slot_end))) {
-                    if (DEFERRED)
-                        __builtin_memcpy(&ring[slot & (PT_RCAP - 1)], &st, 8);
-                    else
-                        ring[slot & (PT_RCAP - 1)] = make_float4(wn.x, wn.y, wn.z, factor);
-                }
+                if (in_mask(kp & __ballot(slot < slot_end)))
+                    ring[slot & (PT_RCAP - 1)] = make_float4(wn.x, wn.y, wn.z, factor);
                 ta += __popcll(A);
                 tk += __popcll(kp);
             };
             int fails_lm = 0; /* lane-major: the consecutive failures after the round */
-            if constexpr (LMAJ) {
+            if constexpr (DEFERRED) {
                 /* Lane-major round: lane l evaluates attempts 8l .. 8l+7, one
                  * chained stream (no jump between its attempts), in packed
                  * pairs.  Child order is attempt order j = 8l + k: the kept
@@ -3149,7 +2964,6 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                 u64 jA, jG;
                 jread(J.j24, lane, jA, jG);
                 const u64 s_lane = jA * rng.st + jG;
-#if PT_LM_BITS
                 /* Per-lane bit planes, attempt k at bit KATT-1-k (one v_addc
                  * each: v + v + the balloted bit): accepted, hemisphere-failed
                  * and kept attempts.  The round's totals, each lane's count of
@@ -3202,6 +3016,8 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                     for (; kb != 0u;) {
                         const int c = __builtin_clz(kb);
                         if (!check || slot < slot_end) {
+                            /* two stores, not one 16-byte one: C2 +8 %, C3 and C5 +-0
+                             * (same-box A/B, profiles/round4/ab_wave_index_ring_split.txt) */
                             float4 *r = &ring[slot & (PT_RCAP - 1)];
                             __builtin_memcpy(r, &s_lane, 8);
                             r->z = __int_as_float(c - (32 - PT_KATT)); /* attempt k of the lane */
@@ -3210,128 +3026,12 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                         kb ^= 0x80000000u >> c;
                     }
                 };
-#if PT_RING_FITS
                 /* the common round: every kept attempt has a free slot (a
                  * wave-uniform test once instead of a compare per entry) */
                 if (tk <= free_slots)
                     put(kbits, false);
                 else
-#endif
                     put(kbits, true);
-#else
-                int tf = 0;
-                u64 Aor = 0ull, K[PT_KATT];
-#if PT_LM_CHAINS == 2
-                /* two independent chains per lane: attempts k and k + KATT/2
-                 * as one packed pair, the second chain starting 3 KATT/2
-                 * draws into the lane's stream (one jump), so the pair's
-                 * engine steps do not wait on each other; tfa / tfb = the
-                 * trailing failures of each half, ab = the lane accepted in
-                 * the second half */
-                constexpr int HK = PT_KATT / 2;
-                u64 sa = s_lane, sb;
-                {
-                    u64 hA, hG;
-                    jread(J.j3, HK, hA, hG);
-                    sb = hA * s_lane + hG;
-                }
-                int tfb = 0, ab = 0;
-#pragma unroll
-                for (int k = 0; k < HK; k++) {
-                    const Attempt2 ap = attempt2_split<KR0>(sa, sb, n, kR);
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const int kk = k + h * HK;
-                        const V3 wn = h ? mk(ap.x.y, ap.y.y, ap.z.y) : mk(ap.x.x, ap.y.x, ap.z.x);
-                        u64 D = 0ull;
-                        if (RAW)
-                            D = dark(wn);
-                        K[kk] = ap.A[h] & ~D;
-                        ta += __popcll(ap.A[h]);
-                        tk += __popcll(K[kk]);
-                        Aor |= ap.A[h];
-                        if (h) {
-                            tfb = zero_if(ap.A[h], add_lane_bit(tfb, ap.F[h]));
-                            ab = mask_sel(ap.A[h], 1, ab);
-                        } else {
-                            tf = zero_if(ap.A[h], add_lane_bit(tf, ap.F[h]));
-                        }
-                    }
-                }
-                tf = ab ? tfb : tf + tfb;
-#else
-                u64 sk = s_lane;
-#pragma unroll
-                for (int k = 0; k < PT_KATT; k += 2) {
-                    const Attempt2 ap = attempt2_chain<KR0>(sk, n, kR);
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const V3 wn = h ? mk(ap.x.y, ap.y.y, ap.z.y) : mk(ap.x.x, ap.y.x, ap.z.x);
-                        u64 D = 0ull;
-                        if (RAW)
-                            D = dark(wn);
-                        K[k + h] = ap.A[h] & ~D;
-                        ta += __popcll(ap.A[h]);
-                        tk += __popcll(K[k + h]);
-                        Aor |= ap.A[h];
-                        tf = zero_if(ap.A[h], add_lane_bit(tf, ap.F[h]));
-                    }
-                }
-#endif
-                /* ring entries, numbered in child order */
-                int slot = nkeep;
-#pragma unroll
-                for (int k = 0; k < PT_KATT; k++)
-                    slot = mbcnt(K[k], slot);
-#pragma unroll
-                for (int k = 0; k < PT_KATT; k++) {
-                    if (in_mask(K[k] & __ballot(slot < slot_end))) {
-                        /* two stores, not one 16-byte one: a float4 of (state, k)
-                         * would be one more 4-register value live across the loop */
-#if PT_RING_SPLIT
-                        float4 *r = &ring[slot & (PT_RCAP - 1)];
-                        __builtin_memcpy(r, &s_lane, 8);
-                        r->z = __int_as_float(k);
-#else
-                        ring[slot & (PT_RCAP - 1)] = make_float4(__uint_as_float((u32)s_lane),
-                                                                 __uint_as_float((u32)(s_lane >> 32)),
-                                                                 __int_as_float(k), 0.0f);
-#endif
-                    }
-                    slot = add_lane_bit(slot, K[k]);
-                }
-                /* failures after the round's last accepted attempt (lane L,
-                 * then every lane above it); none accepted: all of them */
-                const u64 GE = Aor ? ~0ull << (63 - __builtin_clzll(Aor)) : ~0ull;
-                int sf = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++)
-                    sf += __popcll(__ballot((tf >> b) & 1) & GE) << b;
-                fails_lm = Aor ? sf : fails + sf;
-#endif
-            } else if (DEFERRED) {
-                /* pairs of attempts in packed f32 */
-                u64 sk = lane_state();
-#pragma unroll
-                for (int k = 0; k < PT_KATT; k += 2) {
-                    if (k >= katt)
-                        break;
-                    if (k)
-                        sk = A64 * sk + g64inc;
-                    const u64 sk1 = A64 * sk + g64inc;
-                    const Attempt2 ap = attempt2<KR0>(sk, sk1, n, kR);
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const V3 wn = h ? mk(ap.x.y, ap.y.y, ap.z.y) : mk(ap.x.x, ap.y.x, ap.z.x);
-                        u64 D = 0ull;
-                        if (RAW)
-                            D = dark(wn);
-                        write_attempt(ap.A[h], ap.A[h] & ~D, h ? sk1 : sk, wn, 0.0f);
-                        if (k + h == katt - 1)
-                            Alast = ap.A[h], Flast = ap.F[h];
-                    }
-                    sk = sk1;
-                }
             } else {
                 u64 sk = lane_state();
 #pragma unroll
@@ -3341,7 +3041,7 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                     if (k)
                         sk = A64 * sk + g64inc;
                     const Attempt at = attempt<DEFERRED, KR0>(sk, n, kR, sc, sNa, abs_rc, child_leaf_depth);
-                    write_attempt(at.A, at.A, sk, at.wn, at.factor);
+                    write_attempt(at.A, at.A, at.wn, at.factor);
                     nlor |= at.NL;
                     if (k == katt - 1)
                         Alast = at.A, Flast = at.F;
@@ -3361,8 +3061,8 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
              * attempts stay below 1000) -- so every half takes all its
              * accepted attempts, and the consecutive-failure count afterwards
              * is that of the last half, which has an accepted attempt. */
-            if (nlor == 0ull && ta < rem && tk <= free_slots && fails <= 999 - 64 * katt && (LMAJ || Alast != 0ull)) {
-                if (LMAJ) {
+            if (nlor == 0ull && ta < rem && tk <= free_slots && fails <= 999 - 64 * katt && (DEFERRED || Alast != 0ull)) {
+                if (DEFERRED) {
                     fails = fails_lm;
                 } else {
                     const int last = 63 - __builtin_clzll(Alast);
@@ -3466,13 +3166,10 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
         auto fast_lane = [&](int pos, float4 en) -> bool {
             const V3 dir = mk(en.x, en.y, en.z);
             PT_MARK(8);
-#if PT_CTX_VGPR
-            const typename S::Root::Ctx ctx = lds_get_v(*cxp);
-#else
+            /* (read as vector values, kept out of SGPRs: C3 -0.8 %, C2 and C5
+             * +-1 %, same-box A/B, profiles/round4/ab_ctx_vgpr.txt) */
             const typename S::Root::Ctx ctx = lds_get(*cxp);
-#endif
             int fok;
-#if PT_UNION_FUSED && !PT_PASS_PAIR_FALLBACK
             if constexpr (PT_SPH_COMPACT && Compact<typename S::Root>::OK) {
                 bool fh;
                 float t;
@@ -3488,12 +3185,10 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                 }
                 return false;
             }
-#endif
             PrimSpans<S::Root::HI> ps;
             PT_MARK(9);
             S::Root::span(ps, ctx, mkray_unit(dir), e);
             PT_MARK(10);
-#if PT_UNION_FUSED && !PT_PASS_PAIR_FALLBACK
             if constexpr (S::Root::UNION_ONLY) {
                 bool fh;
                 float t;
@@ -3511,18 +3206,13 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                 }
                 return false;
             }
-#endif
             if constexpr (S::Root::NO_DIFF) {
                 /* the union rule over the positive primitives (and empty
-                 * intersections); the pairwise checks only where it cannot
-                 * decide */
+                 * intersections); lanes it cannot decide go to the full merge
+                 * directly, not through the pairwise checks, whose all-pairs
+                 * code raises the pass's register pressure for lanes that are
+                 * rare there */
                 fok = cheap_ok<typename S::Root>(ps);
-#if PT_PASS_PAIR_FALLBACK
-                if (wave_any(!fok)) {
-                    if (!fok)
-                        fok = S::Root::fast_ok(ps);
-                }
-#endif
             } else {
                 fok = S::Root::fast_ok(ps);
             }
@@ -3631,13 +3321,13 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                 if (lane < cf) {
                     float4 en = ring[pos & (PT_RCAP - 1)];
                     if (DEFERRED) {
-                        /* the parked attempt's three draws again (attempt2's
+                        /* the parked attempt's three draws again (attempt2_chain's
                          * arithmetic element by element: the same w), then the
                          * normalisation and factor of path-trace.h:157, :160,
                          * left to this pass so that 64 useful lanes do them */
                         u64 st;
                         __builtin_memcpy(&st, &en, 8);
-                        if (LMAJ) { /* the lane's round state, then 3k draws to attempt k */
+                        { /* the lane's round state, then 3k draws to attempt k */
                             u64 jA, jG;
                             jread(J.j3, __float_as_int(en.z), jA, jG);
                             st = jA * st + jG;
@@ -4832,11 +4522,14 @@ __device__ constexpr int lds_workgroups()
     constexpr int n = 160 * 1024 / alloc;
     return n < 1 ? 1 : n > 5 ? 5 : n;
 }
-/* lane sums in LDS (PT_LSUM_LDS): forced, or where they cost no workgroup per CU */
+/* lane sums in LDS: nowhere.  C2 +1..2.5 % alone, nothing on top of the
+ * recomputed lane index; C3, C5 +-0 (profiles/round4/ab_lane_remat_lsum_lds.txt).
+ * The form stays, as do lsbuf's 16 bytes, which are part of every kernel's
+ * group segment size. */
 template <class S, int MAXD>
 __device__ constexpr bool lsum_lds()
 {
-    return PT_LSUM_LDS < 0 ? lds_workgroups<S, MAXD, true>() == lds_workgroups<S, MAXD, false>() : PT_LSUM_LDS != 0;
+    return false;
 }
 template <class S, int MAXD>
 __device__ constexpr int min_workgroups()

@@ -11,6 +11,8 @@ def test_jobs():
     import zoo
     jobs = [((lambda b=b: pt.DeviceScene(zoo.build(b))), d) for (_, b, _, _, _, d) in zoo.RENDER_CASES]
     jobs += [((lambda b=b: pt.DeviceScene(zoo.build(b))), d) for (b, d) in zoo.GPU_ONLY_CASES]
+    # tests/test_scene_facts.py test_retired_knob_is_a_compile_error (the compile that succeeds)
+    jobs += [((lambda: pt.DeviceScene(zoo.build("scene_p1"))), 4)]
     # tests/test_gpu_parity.py test_fast_spine_bitexact
     jobs += [((lambda b=b: pt.DeviceScene(zoo.build(b), fast_spine=True)), d)
              for (b, d) in [("csg_zoo", 6), ("scene_p1", 8), ("union_zoo", 6)]]

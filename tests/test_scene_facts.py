@@ -175,6 +175,22 @@ def test_pruning_shrinks_the_kernel(built, monkeypatch):
     assert pruned["code_bytes"] < 0.6 * full["code_bytes"], (pruned["code_bytes"], full["code_bytes"])
 
 
+def test_retired_knob_is_a_compile_error(built):
+    """a retired value knob and a retired hook of pt_device.h: defining either
+    fails the compile with an error that names it, instead of building the
+    default under a variant's name; with nothing defined the module compiles"""
+    assert "PT_DEVICE_DEFINES" not in os.environ
+    for defs, knob in [("PT_LM_BITS=0", "PT_LM_BITS"), ("PT_PAD_VALU=4", "PT_PAD_VALU")]:
+        os.environ["PT_DEVICE_DEFINES"] = defs
+        try:
+            with pytest.raises(pt.PtError) as err:
+                pt.DeviceScene(scenes.scene_p1()).compile(4)
+        finally:
+            del os.environ["PT_DEVICE_DEFINES"]
+        assert "retired build-time knob" in str(err.value) and knob in str(err.value), str(err.value)
+    assert pt.DeviceScene(scenes.scene_p1()).compile(4)
+
+
 # ------------------------------------------------------------------- GPU
 
 def against_oracle(root, tmp_path, w, h, spp, depth):
