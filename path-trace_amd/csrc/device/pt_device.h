@@ -1624,6 +1624,186 @@ struct Occl<Uni<A, B>>
     }
 };
 
+/* ---- kept children that end inside a solid (PT_INSIDE_ZERO) ---------------
+ * The inside-solid probe of the first pass.  X is a non-emissive,
+ * untransformed sphere whose path to the root holds only Unions and
+ * Differences entered on their A side, each with a single sphere as its B
+ * side; B(X) is those spheres.  On a lane with a unit child ray the probe
+ * fires when X is live (disc > EPS: the reference's own test on the same
+ * bits), X's exit t1_X is at least EPS, and, going up X's path with L = t0_X
+ * at first, the B sphere of every Difference is dead or lies strictly inside
+ * (L, t1_X), after which L = max(L, t1_B).  Then a point t* just below t1_X
+ * lies inside X and past every boundary of B(X), and:
+ *  1. the root's span list holds a span K with K.start <= t* < K.end, whatever
+ *     the ties elsewhere: a Union (src/union.cpp:84-134) only ever emits an
+ *     input span or a superset of it, so the span S holding t* that it hands
+ *     up still starts at or before L.  A Difference (src/difference.cpp:84-135)
+ *     meets S with its one B span either gone (:93, S passes) or untouched by
+ *     the A spans before S: those end before S.start <= L < B.start and leave
+ *     at :99, and an earlier span that reaches past B.start either takes B
+ *     with it (nextB) or is cut at :113 and leaves B to S.  B cannot be ahead
+ *     of S (:99: S.end > t* > B.end) nor behind it (:105: B.end > B.start >
+ *     S.start), and S.start < B.start takes :109, where S.end > B.end moves
+ *     S.start to B.end < t* (:120).  The branch of :126-130, which for
+ *     B.start <= S.start <= B.end < S.end sets S.END to B.start and so loses
+ *     t*, is the one the lower bound on B.start rules out (an origin inside X
+ *     and the subtractor both, as on the surfaces that very branch makes
+ *     visible inside a cavity, would otherwise see through X).  S is emitted
+ *     once B is gone, starting at or before the new L.  K.end >= t1_X >= EPS,
+ *     so K qualifies in traceRay's scan (include/path-trace.h:66-96);
+ *  2. the scan's answer is zero, given (compile time, ok()) that every plane
+ *     hangs off the root through Unions only, that there is no emissive
+ *     sphere, no transformed node, no user object and no Intersection on X's
+ *     path, and (per burst) that the origin is outside every emissive plane
+ *     (T_E > 0, the bound of Occl<Pln>::emis_lb, here as the minimum over a
+ *     tree with Differences: they hold no plane) and every sphere's far bound
+ *     |o - c| + r is below T_E.  Every boundary that can start a span at or
+ *     before t* is then non-emissive: emissive spans start at >= T_E, and at
+ *     the Union where one joins, every span made of sphere boundaries ends
+ *     before it and is emitted first.  A span that starts before eps ends on a
+ *     non-emissive boundary or runs to max_value (:82); a receding emissive
+ *     plane's end is negative.  So the scan stops on a non-emissive material or
+ *     returns black: the term ((aN * factor) * rc) * (+0, +0, +0) is zero for
+ *     the finite weights wfin asks for, and zero terms change no lane sum of
+ *     the fast order.  Reference-order bursts (STRICT) do not take the rule.
+ * Bounds are compared as numerators n = -b -+ sqrt(disc): the reference's
+ * t = fl(N / a), N = fl(-b -+ SQ) with the correctly rounded root SQ, and
+ * division by the ray's one positive a is monotone.  b and disc are the bits
+ * clear_mask (and the reference) compute; the raw v_sqrt_f32 is within one
+ * ulp of SQ.  With G >= |o - c| + r for every sphere (|b| <= G (1 + 2^-20),
+ * SQ <= 1.5 G, |N| <= 2.6 G; all finite: G <= T_E <= 1e15):
+ *   |n - N| <= 2^-22 SQ + 2 * 2^-24 * 2.6 G < 6.7e-7 G,
+ * and fl(N' / a) < fl(N / a) as soon as N - N' > 2^-23 * 2.7 G, so
+ * n > n' + 1.7e-6 G decides it; mg = 1e-5 G is used.  t1_X >= EPS follows
+ * from N_X >= EPS (1 + 2^-19): n1_X > EPS * 1.001 + mg.
+ * A node hands up its own bounds as a subtractor -- bmin and bmax, the entry
+ * and exit numerators of a live sphere, (+inf, -inf) for a dead one and
+ * (-inf, +inf), which no candidate passes, for anything else -- and its best
+ * candidate: xbest, the largest exit numerator among those that passed the
+ * subtractor tests so far (-inf: none), and xlo, that candidate's L. */
+#ifndef PT_INSIDE_ZERO
+#define PT_INSIDE_ZERO 1
+#endif
+struct InsideG /* burst-uniform margins */
+{
+    float mg, xmin;
+};
+struct InsideV
+{
+    float bmin, bmax, xbest, xlo;
+};
+template <class N>
+struct Inside /* transformed nodes, user objects: the rule is compiled out */
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return false; }
+    template <class SEL>
+    __device__ static constexpr bool sph_only() { return false; }
+};
+template <int P, int O, int M>
+struct Inside<Sph<P, O, M>>
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return !SEL::take(M); }
+    template <class SEL>
+    __device__ static constexpr bool sph_only() { return !SEL::take(M); }
+    template <class SEL>
+    __device__ static __forceinline__ float emis_lb(const typename Sph<P, O, M>::Ctx &, const Env &)
+    {
+        return __builtin_inff();
+    }
+    /* |o - c|^2 + r^2: (|o - c| + r)^2 is at most twice that */
+    __device__ static __forceinline__ float far2(const typename Sph<P, O, M>::Ctx &c, const Env &e)
+    {
+        return c.c + 2.0f * e.P[O + 3];
+    }
+    __device__ static __forceinline__ InsideV eval(const typename Sph<P, O, M>::Ctx &c, const Ray &q, const InsideG &g)
+    {
+        const float b = dot(c.omc, q.d);
+        const float disc = b * b - q.a * c.c;
+        const float sq = __builtin_amdgcn_sqrtf(disc);
+        const bool dead = disc <= EPS;
+        InsideV v;
+        v.bmin = dead ? __builtin_inff() : -b - sq;
+        v.bmax = dead ? -__builtin_inff() : -b + sq;
+        v.xbest = v.bmax > g.xmin ? v.bmax : -__builtin_inff();
+        v.xlo = v.bmin;
+        return v;
+    }
+};
+template <int P, int O, int M, int AX, int U>
+struct Inside<Pln<P, O, M, AX, U>>
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return true; }
+    template <class SEL>
+    __device__ static constexpr bool sph_only() { return false; }
+    template <class SEL>
+    __device__ static __forceinline__ float emis_lb(const typename Pln<P, O, M, AX, U>::Ctx &c, const Env &e)
+    {
+        return Occl<Pln<P, O, M, AX, U>>::template emis_lb<SEL>(c, e);
+    }
+    __device__ static __forceinline__ float far2(const typename Pln<P, O, M, AX, U>::Ctx &, const Env &) { return 0.0f; }
+    __device__ static __forceinline__ InsideV eval(const typename Pln<P, O, M, AX, U>::Ctx &, const Ray &, const InsideG &)
+    {
+        return {-__builtin_inff(), __builtin_inff(), -__builtin_inff(), 0.0f};
+    }
+};
+#define PTD_INSIDE_COMMON(NODE)                                                                                  \
+    template <class SEL>                                                                                         \
+    __device__ static constexpr bool sph_only()                                                                  \
+    {                                                                                                            \
+        return Inside<A>::template sph_only<SEL>() && Inside<B>::template sph_only<SEL>();                       \
+    }                                                                                                            \
+    template <class SEL>                                                                                         \
+    __device__ static __forceinline__ float emis_lb(const typename NODE<A, B>::Ctx &c, const Env &e)             \
+    {                                                                                                            \
+        return fminf(Inside<A>::template emis_lb<SEL>(c.a, e), Inside<B>::template emis_lb<SEL>(c.b, e));        \
+    }                                                                                                            \
+    __device__ static __forceinline__ float far2(const typename NODE<A, B>::Ctx &c, const Env &e)                \
+    {                                                                                                            \
+        return fmaxf(Inside<A>::far2(c.a, e), Inside<B>::far2(c.b, e));                                          \
+    }
+template <class A, class B>
+struct Inside<Uni<A, B>>
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return Inside<A>::template ok<SEL>() && Inside<B>::template ok<SEL>(); }
+    PTD_INSIDE_COMMON(Uni)
+    __device__ static __forceinline__ InsideV eval(const typename Uni<A, B>::Ctx &c, const Ray &q, const InsideG &g)
+    {
+        const InsideV a = Inside<A>::eval(c.a, q, g), b = Inside<B>::eval(c.b, q, g);
+        const bool ta = a.xbest >= b.xbest;
+        return {-__builtin_inff(), __builtin_inff(), ta ? a.xbest : b.xbest, ta ? a.xlo : b.xlo};
+    }
+};
+template <class A, class B>
+struct Inside<Diff<A, B>>
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return sph_only<SEL>(); }
+    PTD_INSIDE_COMMON(Diff)
+    __device__ static __forceinline__ InsideV eval(const typename Diff<A, B>::Ctx &c, const Ray &q, const InsideG &g)
+    {
+        const InsideV a = Inside<A>::eval(c.a, q, g), b = Inside<B>::eval(c.b, q, g);
+        const bool pass = a.xbest > b.bmax + g.mg && b.bmin > a.xlo + g.mg;
+        return {-__builtin_inff(), __builtin_inff(), pass ? a.xbest : -__builtin_inff(), fmaxf(a.xlo, b.bmax)};
+    }
+};
+template <class A, class B>
+struct Inside<Isect<A, B>>
+{
+    template <class SEL>
+    __device__ static constexpr bool ok() { return sph_only<SEL>(); }
+    PTD_INSIDE_COMMON(Isect)
+    /* no candidate, and no subtractor a candidate passes */
+    __device__ static __forceinline__ InsideV eval(const typename Isect<A, B>::Ctx &, const Ray &, const InsideG &)
+    {
+        return {-__builtin_inff(), __builtin_inff(), -__builtin_inff(), 0.0f};
+    }
+};
+#undef PTD_INSIDE_COMMON
+
 /* How often the reference negates the normal of a boundary of primitive `prim`
  * on its way up through node N: a Difference hands A's boundaries through and
  * takes B's by copyEndFromStart / copyStartFromEnd (src/difference.cpp:113-128),
@@ -2888,6 +3068,26 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
         const float bw = (KR0 ? 1.0f : 1.0f + length(kR)) * 1.0001f;
         occ_g = unif(te > 0.0f ? bw * 1.001f / te : __builtin_inff());
     }
+    /* kept children that end inside a solid have a zero term (Inside,
+     * PT_INSIDE_ZERO): the first pass settles them.  Its burst-uniform gates:
+     * finite weights, the origin outside every emissive plane (T_E > 0) and
+     * every sphere's far bound below T_E, (|o - c| + r)^2 <= 2 far2 < T_E^2;
+     * G = sqrt(2.02 far2) scales the margins */
+#if PT_INSIDE_ZERO
+    constexpr bool INS = CLEAR && !STRICT && Inside<typename S::Root>::template ok<Emissive<S>>();
+#else
+    constexpr bool INS = false;
+#endif
+    InsideG ins_g = {0.0f, 0.0f};
+    int ins_on = 0;
+    if constexpr (INS) {
+        const float te = fminf(Inside<typename S::Root>::template emis_lb<Emissive<S>>(c0, e), 1e15f);
+        const float g2 = 2.02f * Inside<typename S::Root>::far2(c0, e);
+        const float g = __builtin_sqrtf(g2);
+        ins_on = uni((wfin && te > 0.0f && g2 < te * te) ? 1 : 0);
+        ins_g.mg = unif(1e-5f * g);
+        ins_g.xmin = unif(EPS * 1.001f + 1e-5f * g);
+    }
     auto dark = [&](V3 wn) -> u64 {
         u64 d = S::Root::template dark_mask<Emissive<S>>(c0, wn, e);
         if constexpr (OCC)
@@ -3360,6 +3560,16 @@ __device__ __forceinline__ int burst_t(const Env &e, Rng &rng, const u64 *__rest
                                 const V3 term = ((aN * en.w) * rc) * col;
                                 ring[pos & (PT_RCAP - 1)] = make_float4(term.x, term.y, term.z, 0.0f);
                                 park = 0;
+                            }
+                            if constexpr (INS) {
+                                /* the inside-solid probe on clear_mask's b and disc */
+                                if (ins_on) {
+                                    const InsideV iv = Inside<typename S::Root>::eval(ctx, q, ins_g);
+                                    if (park && iv.xbest > 0.0f) {
+                                        ring[pos & (PT_RCAP - 1)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                                        park = 0;
+                                    }
+                                }
                             }
                             PT_MARK(17);
                         }
