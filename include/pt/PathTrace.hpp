@@ -765,6 +765,22 @@ public:
         p.spp = spp, p.depth = depth, p.seed = seed, p.order = order, p.ray_begin = ray_begin;
         ptCheck(pt_trace_rays(q_->s, &p, rays, n, rgb, nullptr));
     }
+    /* the chained calls' device side: one chain of n entries -- pixel indices
+     * or rays of 7 floats -- on the engine state `state`, which comes back as
+     * the chain left it (pt_trace_chains) */
+    void renderChain(const int32_t *pixels, const float *rays, int64_t n, int W, int H, int spp, int depth, float sw,
+                     float sh, float dist, uint64_t &state, float *rgb) const
+    {
+        if (!root_set_) {
+            ptCheck(pt_set_root(q_->s, q_->id));
+            root_set_ = true;
+        }
+        pt_chain_params p = {};
+        p.width = W, p.height = H, p.spp = spp, p.depth = depth;
+        p.screen_w = sw, p.screen_h = sh, p.screen_dist = dist;
+        const int64_t begin[2] = {0, n};
+        ptCheck(pt_trace_chains(q_->s, &p, pixels, rays, begin, 1, &state, rgb, nullptr, nullptr));
+    }
     const Span &operator*() const override { return spans_.at(k_); }
     const Span *operator->() const override { return &spans_.at(k_); }
     bool isAtEnd() const override { return k_ >= spans_.size(); }
@@ -811,9 +827,10 @@ const float DefaultScreenWidth = 4.0 / 3.0, DefaultScreenHeight = 1.0, DefaultSc
  * public members: the 64-bit LCG v = 214013 v + 2531011, output v >> 32,
  * seed(s) setting v = s ^ 0x12476242.  state() is the one extension: the
  * engine's v, for saving and restoring a stream.  Passed to tracePixel /
- * traceRay it is an engine type T like any other (two of its draws seed the
- * call, below): the device does not yet run a call's samples draw by draw on
- * the caller's state, which is what the reference does with this engine. */
+ * traceRay it is what it is in the reference: every sample of the call draws
+ * from it in sequence and the call leaves it where the reference would (the
+ * DefaultRandomEngine overloads below, pt_trace_chains), so a program that
+ * threads one engine through its pixels gets the reference's bits. */
 class DefaultRandomEngine
 {
 public:
@@ -950,8 +967,8 @@ inline Color tracePixel(SpanIterator &spanIterator, int px, int py, int screenXR
 }
 
 /* Any other engine type T (unsigned operator()(), as include/vector3d.h:14-34
- * requires of it -- e.g. the reference's DefaultRandomEngine): two of its
- * draws make the run seed of this call, so successive calls see fresh
+ * requires of it; DefaultRandomEngine has overloads of its own, below): two of
+ * its draws make the run seed of this call, so successive calls see fresh
  * streams as with the reference's shared engine. */
 template <typename T>
 inline Color tracePixel(SpanIterator &spanIterator, int px, int py, int screenXResolution, int screenYResolution,
@@ -1055,6 +1072,90 @@ inline Color tracePixel(SpanIterator &spanIterator, float px, float py, float sc
     FrameEngine e((hi << 32) | lo);
     return tracePixel(spanIterator, px, py, screenXResolution, screenYResolution, sampleCount, rayDepth, screenWidth,
                       screenHeight, screenDistance, e);
+}
+
+/* The reference's own engine in the reference's own way (include/path-trace.h:
+ * 187-201 with T = DefaultRandomEngine): every sample of every pixel draws
+ * from the caller's engine in sequence, each starting where the one before
+ * left it, and the engine ends where the reference's would -- the results are
+ * the reference's bit for bit.  colors[k] = tracePixel of pixel (px[k], py[k]),
+ * k = 0 .. n - 1 in that order on the one engine: a chain (pt_trace_chains).  A
+ * chain's samples cannot run side by side, so this is the mode for comparing
+ * pixels with a reference build, not for rendering frames; it is worth handing
+ * over as many pixels per call as the program has. */
+inline void tracePixelsChained(SpanIterator &spanIterator, const int *px, const int *py, size_t n,
+                               int screenXResolution, int screenYResolution, int sampleCount, int rayDepth,
+                               float screenWidth, float screenHeight, float screenDistance,
+                               DefaultRandomEngine &randomEngine, Color *colors)
+{
+    DeviceSpanIterator &it = deviceIterator(spanIterator, "tracePixel");
+    if (n == 0)
+        return;
+    static_assert(sizeof(Color) == 3 * sizeof(float), "Color must be 3 packed floats");
+    std::vector<int32_t> pix(n);
+    for (size_t k = 0; k < n; k++) {
+        if (px[k] < 0 || px[k] >= screenXResolution || py[k] < 0 || py[k] >= screenYResolution)
+            throw std::invalid_argument("tracePixel: a chained pixel must lie inside the frame");
+        pix[k] = (int32_t)pixelKeyIndex(px[k], py[k], screenXResolution);
+    }
+    uint64_t state = randomEngine.state();
+    it.renderChain(pix.data(), nullptr, (int64_t)n, screenXResolution, screenYResolution, sampleCount, rayDepth,
+                   screenWidth, screenHeight, screenDistance, state, reinterpret_cast<float *>(colors));
+    randomEngine.state(state);
+}
+
+inline Color tracePixel(SpanIterator &spanIterator, int px, int py, int screenXResolution, int screenYResolution,
+                        int sampleCount, int rayDepth, float screenWidth, float screenHeight, float screenDistance,
+                        DefaultRandomEngine &randomEngine)
+{
+    Color c;
+    tracePixelsChained(spanIterator, &px, &py, 1, screenXResolution, screenYResolution, sampleCount, rayDepth,
+                       screenWidth, screenHeight, screenDistance, randomEngine, &c);
+    return c;
+}
+
+/* sampleCount traceRay<DefaultRandomEngine> values of rays[0 .. n), ray after
+ * ray on the one engine, each ray's mean in colors (n = 1: the sample loop of
+ * include/path-trace.h:178-183) */
+inline void traceRaysChained(SpanIterator &spanIterator, const Ray *rays, const float *strengths, size_t n,
+                             int sampleCount, int rayDepth, DefaultRandomEngine &randomEngine, Color *colors)
+{
+    DeviceSpanIterator &it = deviceIterator(spanIterator, "traceRay");
+    if (n == 0)
+        return;
+    std::vector<float> r(7 * n);
+    for (size_t k = 0; k < n; k++) {
+        const float v[7] = {rays[k].origin.x, rays[k].origin.y, rays[k].origin.z, rays[k].dir.x,
+                            rays[k].dir.y,    rays[k].dir.z,    strengths ? strengths[k] : 1.0f};
+        std::copy(v, v + 7, &r[7 * k]);
+    }
+    uint64_t state = randomEngine.state();
+    it.renderChain(nullptr, r.data(), (int64_t)n, 1, 1, sampleCount, rayDepth, 1.0f, 1.0f, 1.0f, state,
+                   reinterpret_cast<float *>(colors));
+    randomEngine.state(state);
+}
+
+/* traceRay<DefaultRandomEngine> (include/path-trace.h:58-165) on the caller's engine; the value comes
+ * back as (0 + c) / 1, so a -0 channel reads +0 */
+inline Color traceRay(const Ray &ray, SpanIterator &spanIterator, int depth, DefaultRandomEngine &randomEngine,
+                      float strength = 1.0f)
+{
+    Color c;
+    traceRaysChained(spanIterator, &ray, &strength, 1, 1, depth, randomEngine, &c);
+    return c;
+}
+
+/* tracePixel's float-coordinate overload (include/path-trace.h:172-185) on the caller's engine */
+inline Color tracePixel(SpanIterator &spanIterator, float px, float py, float screenXResolution,
+                        float screenYResolution, int sampleCount, int rayDepth, float screenWidth, float screenHeight,
+                        float screenDistance, DefaultRandomEngine &randomEngine)
+{
+    const float x = 2 * px / screenXResolution - 1;
+    const float y = 1 - 2 * py / screenYResolution;
+    const Ray ray(Vector3D(0, 0, 0), Vector3D(x * screenWidth, y * screenHeight, -screenDistance));
+    Color c;
+    traceRaysChained(spanIterator, &ray, nullptr, 1, sampleCount, rayDepth, randomEngine, &c);
+    return c;
 }
 
 /* Coalesces the per-pixel tracePixel calls of many host threads into device

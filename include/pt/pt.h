@@ -331,6 +331,42 @@ int pt_trace_rays(pt_scene *s, const pt_trace_params *p, const float *rays, int6
  * and depth without touching a GPU. */
 int pt_trace_compile(pt_scene *s, int depth);
 
+/* Chained rendering: the reference's one deterministic mode, a program that
+ * owns a single DefaultRandomEngine and calls tracePixel / traceRay with it
+ * entry after entry, every sample starting where the one before left the
+ * engine.  A chain is such a sequence: entries begin[c] .. begin[c + 1] - 1 of
+ * `pixels` (indices py * width + px; each entry is tracePixel<T>'s int
+ * overload, include/path-trace.h:187-201) or of `rays` (7 floats as for
+ * pt_trace_rays; each entry is the sample loop of :178-183 over traceRay<T>
+ * with the ray's strength), with ONE engine threaded through every sample of
+ * every entry, starting from states[c] (DefaultRandomEngine's 64-bit state v,
+ * the recurrence of include/pt/pt_engine.h; seed(x) leaves (uint32_t)x ^
+ * 0x12476242).  Exactly one of pixels / rays is given.
+ * Chains are independent of each other and run side by side; a chain's samples
+ * run one after another, so the call issues max(entries of a chain) x spp
+ * launches of the chained module, each tracing at most one sample of every
+ * chain in the reference's order.  Results are the reference's bit for bit:
+ * rgb_out[3e..] = entry e's colour, state_after[e] = the engine's state after
+ * entry e (may be NULL), states[c] = after chain c's last entry (an empty
+ * chain's stays as given).  A chain cut in two calls, the second starting from
+ * the first's returned state, gives the same results as one call.
+ * Arguments are checked before any device is touched: PT_ERR_ARG names the
+ * argument in pt_last_error(). */
+typedef struct pt_chain_params {
+    int width, height;             /* screenXResolution, screenYResolution (pixels only)        */
+    int spp;                       /* sampleCount (>= 1)                                        */
+    int depth;                     /* rayDepth                                                  */
+    float screen_w, screen_h, screen_dist; /* pixels only                                       */
+    int device;                    /* HIP device ordinal                                        */
+} pt_chain_params;
+int pt_trace_chains(pt_scene *s, const pt_chain_params *p, const int32_t *pixels, const float *rays,
+                    const int64_t *begin, int64_t nchains, uint64_t *states, float *rgb_out,
+                    uint64_t *state_after, pt_render_stats *stats);
+/* JIT-compile (or fetch from the cache) pt_trace_chains' module for this scene
+ * and depth -- the pixel kind, or with rays != 0 the ray kind -- without
+ * touching a GPU. */
+int pt_chain_compile(pt_scene *s, int depth, int rays);
+
 /* Everything a render with p needs -- code object loaded, scene parameters
  * and images uploaded, staging buffers allocated -- without rendering, so a
  * timed or latency-sensitive render does no compilation or allocation. */
@@ -393,6 +429,10 @@ int pt_scene_set_split(pt_scene *s, int on);
  * the compiler options and the hiprtc version -- the file name of its entry in
  * the code-object cache (hex string, thread-local storage). */
 const char *pt_scene_kernel_key(pt_scene *s, int depth);
+/* The same for any of the scene's module kinds: rays != 0 the ray-list module
+ * of pt_trace_rays, chain != 0 the chained module of pt_trace_chains (with
+ * rays, its ray kind); both 0 is pt_scene_kernel_key. */
+const char *pt_scene_module_key(pt_scene *s, int depth, int rays, int chain);
 /* What code generation proved about the scatter bursts this scene's materials
  * can reach; the render kernel is compiled with only those variants.
  * *kr_reach: bit 0 = a burst with scatter coefficient exactly 1 is possible,

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpt.so")
-SOURCES = ["runtime.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp"]
+SOURCES = ["runtime.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp", "chain.cpp"]
 HEADERS = ["internal.h", "device/pt_device.h", "../../include/pt/pt.h", "../../include/pt/pt_engine.h"]
 
 

@@ -404,7 +404,7 @@ uint64_t fnv1a(const std::string &s, uint64_t h = 1469598103934665603ull)
 
 } // namespace
 
-Generated generate(const SceneImpl &s, int depth, bool rays)
+Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
 {
     if (s.root < 0)
         throw Error(PT_ERR_ARG, "scene has no root object (pt_set_root)");
@@ -473,6 +473,13 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     /* the ray-list module of pt_trace_rays: items are caller rays, not camera samples */
     if (rays)
         src << "#define PT_RAYS 1\n";
+    /* the chained module of pt_trace_chains: one launch traces one sample of each chain on the
+     * chain's own engine state (pt_device.h PT_CHAIN).  Built as the scene's default render module
+     * is -- lane_sample plus lane resume or the wave walk -- whatever lane walk the scene asks for */
+    if (chain)
+        src << "#define PT_CHAIN 1\n";
+    const int lane_walk = chain ? 0 : s.lane_walk;
+    const bool lane_scatter = !chain && s.lane_scatter;
     /* per-scene occupancy (pt_scene_set_occupancy): the launch bounds' workgroups per CU */
     if (s.wg_per_cu > 0)
         src << "#define PT_MIN_WAVES " << s.wg_per_cu << "\n";
@@ -480,10 +487,10 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     if (s.fast_spine)
         src << "#define PT_FAST_SPINE 1\n";
     /* per-scene lane walk of scatter-free trees (pt_scene_set_lane_walk) */
-    if (s.lane_walk > 0)
-        src << "#define PT_LANE_WALK " << s.lane_walk << "\n";
+    if (lane_walk > 0)
+        src << "#define PT_LANE_WALK " << lane_walk << "\n";
     /* per-scene lane walk with scatter loops (pt_scene_set_lane_scatter) */
-    if (s.lane_scatter)
+    if (lane_scatter)
         src << "#define PT_LANE_SCATTER 1\n";
     /* per-scene resumable lane walk (pt_scene_set_lane_resume): lanes walk
      * their whole trees and ask the wave for each burst.  Only where no burst
@@ -491,8 +498,8 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
      * for elsewhere, the module is built without it.  Auto (-1) follows
      * LANE_RESUME_AUTO, decided by the C3 measurement */
     constexpr bool LANE_RESUME_AUTO = true;
-    if ((s.lane_resume < 0 ? LANE_RESUME_AUTO : s.lane_resume > 0) && bursts_all_leaf && s.lane_walk == 0 &&
-        !s.lane_scatter)
+    if ((s.lane_resume < 0 ? LANE_RESUME_AUTO : s.lane_resume > 0) && bursts_all_leaf && lane_walk == 0 &&
+        !lane_scatter)
         src << "#define PT_LANE_RESUME 1\n";
     /* Difference-free trees skip a sphere's root and divisions when no lane of
      * the wave meets it (pt_device.h PT_SPHERE_SKIP; same-box A/B,
@@ -511,7 +518,7 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
      * next chunk's dequeue in flight while a chunk is traced (round 6, on the
      * final kernel: +0.4 %, 6 of 6 same-box pairs at 1 024 spp,
      * profiles/round6/ab_dequeue_prefetch_c3.txt; round 4's kernel: -0.5 %) */
-    else if (s.lane_walk == 0 && !s.lane_scatter)
+    else if (lane_walk == 0 && !lane_scatter)
         src << "#ifndef PT_KATT\n#define PT_KATT 10\n#endif\n"
             << "#ifndef PT_DEQUEUE_PREFETCH\n#define PT_DEQUEUE_PREFETCH 1\n#endif\n";
     /* ... and are scheduled by the iterative max-occupancy strategy (same-box
@@ -519,9 +526,9 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
      * profiles/round5/ab_sched_maxocc.txt); not when the PT_JIT_OPTIONS hook
      * names a strategy of its own (an LLVM option may occur once) */
     const char *jit_opts = getenv("PT_JIT_OPTIONS");
-    const bool maxocc = root.find("Diff<") != std::string::npos && s.lane_walk == 0 && !s.lane_scatter &&
+    const bool maxocc = root.find("Diff<") != std::string::npos && lane_walk == 0 && !lane_scatter &&
                         !(jit_opts && strstr(jit_opts, "sched-strategy"));
-    src << device_library_source() << "\n";
+    src << device_library_source(chain) << "\n";
     if (!g.user_obj.empty())
         src << device_user_object_source() << "\n";
     if (g.multi_span)
@@ -585,7 +592,7 @@ Generated generate(const SceneImpl &s, int depth, bool rays)
     src << "  __device__ static __forceinline__ float ior(int m, const Env &e) { return e.P[" << ior_off
         << " + m]; }\n";
     src << "};\n} // namespace ptgen\n";
-    src << "PT_DEFINE_KERNELS(ptgen::Scene, " << maxd << ")\n";
+    src << (chain ? "PT_DEFINE_CHAIN_KERNEL" : "PT_DEFINE_KERNELS") << "(ptgen::Scene, " << maxd << ")\n";
 
     Generated out;
     out.source = src.str();

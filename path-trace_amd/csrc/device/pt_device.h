@@ -101,6 +101,22 @@ struct PtLaunch
                            chunk of the launch)                                   */
     unsigned *bail;     /* split launches: the light kernel appends the chunks it
                            leaves to the full kernel here (count: stats[35])      */
+#ifdef PT_CHAIN
+    /* Chained modules (pt_trace_chains): one launch is one STEP, at most one
+     * sample of each chain, on the chain's own DefaultRandomEngine state instead
+     * of a keyed one.  Item k of the step is chain c = order[k], its entry
+     * e = begin[c] + step / spp (the pixel list's entry e, or lp.rays' ray e) and
+     * its sample s = step % spp.  nsamp = 1 and slot-major per-sample output are
+     * set by the runtime; the stage buffer and pt_reduce are not used. */
+    u64 *states;            /* per chain: the engine state, read at the item's start, written at its end */
+    const int *order;       /* chain ids by descending step count: a step's chains are a prefix */
+    const long long *begin; /* per chain: its first entry */
+    int step, spp;
+    float *acc;             /* per chain: tracePixel's running sum of the entry's samples */
+    float *rgb;             /* per entry: sum / spp, written with its last sample */
+    u64 *state_after;       /* per entry: the engine state after its last sample */
+    u64 *work;              /* this step's chunk counter (one per step, zeroed once) */
+#endif /* PT_CHAIN */
 };
 /* The engine key index of a slot's item: its pixel index, or in a ray-list
  * module the caller's ray index */
@@ -4304,10 +4320,16 @@ __device__ __forceinline__ bool lane_walk_sc(const Env &e, int depth0, V3 o0, V3
 template <class S, int MAXD, bool STRICT>
 __device__ __forceinline__ V3 trace_sample(const Env &e, const PtLaunch &lp, int pix, int s, Frame *F, const WaveLds &L,
                                            const u64 *__restrict__ jump, const JumpLds &jl, Counters &cnt,
+#ifdef PT_CHAIN
+                                           u64 &chain_state, /* in: the chain's engine; out: after the sample */
+#endif /* PT_CHAIN */
                                            const CamHit &cam)
 {
     Rng rng;
     rng_seed(rng, lp.seed, PT_ITEM_KEY(lp, pix), (u64)s);
+#ifdef PT_CHAIN
+    rng.st = chain_state;
+#endif /* PT_CHAIN */
 #ifdef PT_RAYS
     /* traceRay(ray, it, depth, engine, strength): the caller's ray, no camera draws */
     {
@@ -4476,6 +4498,9 @@ __device__ __forceinline__ V3 trace_sample(const Env &e, const PtLaunch &lp, int
             }
         }
     }
+#ifdef PT_CHAIN
+    chain_state = rng.st;
+#endif /* PT_CHAIN */
     /* tracePixel with one sample: (Color(0,0,0) + traceRay(...)) / 1 */
     V3 z = mk(0, 0, 0);
     return (z + result) / 1.0f;
@@ -4835,6 +4860,9 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
     /* Split launches (lane-walk scenes, see pt_render_light): the full kernel
      * serves the light kernel's list, with its own counter (stats[36]) */
     u64 *work = stats + (lp.list ? 36 : 15); /* chunk counter, zeroed before every launch */
+#ifdef PT_CHAIN
+    work = lp.work;
+#endif /* PT_CHAIN */
     const long long n_idx = lp.list ? (long long)(u32)uni((int)(u32)stats[35]) : n_chunks;
     /* The queue is one device-scope counter of chunks.  A single address takes
      * on the order of 10^8 atomics per second across the 8 XCDs, which caps
@@ -4912,6 +4940,9 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
         int lpix = 0, ls = 0; /* the lane's (pixel, sample), read by the wave loop below */
         [[maybe_unused]] int rsp = 0; /* PT_LANE_RESUME: the lane's frames */
         [[maybe_unused]] u64 lrng = 0; /* ... and its engine after the camera draws */
+#ifdef PT_CHAIN
+        u64 cst = 0; /* the lane's chain engine: after the camera draws, then after the sample */
+#endif /* PT_CHAIN */
         V3 lres = mk(0, 0, 0);
         const bool lvalid = lane < CH && item0 + lane < lp.n_items;
         if (lvalid) {
@@ -4919,10 +4950,17 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
             long long slot;
             int s;
             item_slot(lp, item, slot, s);
+#ifdef PT_CHAIN
+            const int chain = lp.order[item];
+            slot = lp.begin[chain] + lp.step / lp.spp, s = lp.step % lp.spp;
+#endif /* PT_CHAIN */
             const int pix = pixels ? pixels[slot] : (int)slot;
             lpix = pix, ls = s;
             Rng r;
             rng_seed(r, lp.seed, PT_ITEM_KEY(lp, pix), (u64)s);
+#ifdef PT_CHAIN
+            r.st = lp.states[chain];
+#endif /* PT_CHAIN */
             typename S::Root::Ctx ctx;
 #ifdef PT_RAYS
             /* the caller's ray (pixels == nullptr: pix is the ray's index) */
@@ -4935,6 +4973,9 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
             const float str = 1.0f;
             S::Root::prep(ctx, o, e);
 #endif
+#ifdef PT_CHAIN
+            cst = r.st; /* a sample its lane finishes draws nothing more (lane_sample) */
+#endif /* PT_CHAIN */
             bool ex = false;
 #ifdef PT_LANE_WALK
             if constexpr (LIGHT) {
@@ -5027,6 +5068,10 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
                     int q = 0, h = 0;
                     st = lane_walk_rs<S>(e, RF, rsp, wr, q, h);
                     const u32 n = lb[lane].z + ((u32)q | ((u32)h << 16));
+#ifdef PT_CHAIN
+                    if (st == RS_DONE) /* the engine its last burst left, before the result takes the slot */
+                        cst = ((u64)lb[lane].y << 32) | (u64)lb[lane].x;
+#endif /* PT_CHAIN */
                     if (st == RS_DONE)
                         lb[lane] = make_uint4(__float_as_uint(wr.x), __float_as_uint(wr.y), __float_as_uint(wr.z), n);
                     else
@@ -5098,8 +5143,19 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
             const uint4 q = lb[j];
             const int qy = uni((int)q.y);
             const CamHit cam = {(qy >> 30) & 1, unif(__uint_as_float(q.z)), (u32)uni((int)q.w), (int)((u32)qy >> 31)};
+#ifdef PT_CHAIN
+            /* the wave draws the sample's camera numbers again, from the chain's state as the launch found it */
+            u64 wst = lp.states[lp.order[item0 + j]];
+#endif /* PT_CHAIN */
             V3 c = trace_sample<S, MAXD, STRICT>(e, lp, uni((int)q.x), qy & 0x3FFFFFFF, stk[wave], L, jump, jl, cnt,
+#ifdef PT_CHAIN
+                                                 wst,
+#endif /* PT_CHAIN */
                                                  cam);
+#ifdef PT_CHAIN
+            if (lane == j)
+                cst = wst;
+#endif /* PT_CHAIN */
             PT_ACC(cnt, 6, tt);
             if (lane == j)
                 lb[j] = make_uint4(__float_as_uint(c.x), __float_as_uint(c.y), __float_as_uint(c.z), 0u);
@@ -5120,6 +5176,32 @@ __device__ __forceinline__ void render_chunk(const float *__restrict__ P, const 
         next = dequeue();
 #endif
         const long long my = item0 + lane;
+#ifdef PT_CHAIN
+        if (lvalid) {
+            /* tracePixel's own sequence for the chain's entry (path-trace.h:191-199): the sum starts at
+             * Color(0, 0, 0), takes one sample per step and is divided by the count after the last; the
+             * engine goes back for the chain's next step.  A chain is one item of a launch at most, so
+             * its lane is the only reader and writer of its sum and state. */
+            const int chain = lp.order[my];
+            const long long entry = lp.begin[chain] + lp.step / lp.spp;
+            const int s = lp.step % lp.spp;
+            float *a = lp.acc + 3 * (long long)chain;
+            V3 sum = mk(0, 0, 0);
+            if (s != 0)
+                sum = mk(a[0], a[1], a[2]);
+            sum = sum + mine;
+            if (s == lp.spp - 1) {
+                const float n = (float)lp.spp;
+                lp.rgb[3 * entry + 0] = sum.x / n;
+                lp.rgb[3 * entry + 1] = sum.y / n;
+                lp.rgb[3 * entry + 2] = sum.z / n;
+                lp.state_after[entry] = cst;
+            } else {
+                a[0] = sum.x, a[1] = sum.y, a[2] = sum.z;
+            }
+            lp.states[chain] = cst;
+        } else
+#endif /* PT_CHAIN */
         if (bailed) {
             /* the full kernel writes this chunk */
         } else if (lp.block_sums) {
@@ -5295,6 +5377,14 @@ __device__ __forceinline__ void tex_eval(const Env &e, const float *__restrict__
 #define PT_DEFINE_LIGHT(SCENE, MAXD)
 #endif
 
+#ifdef PT_CHAIN
+/* A chained module has the reference-order kernel alone: a chain's samples are the reference's own sequence */
+#define PT_DEFINE_CHAIN_KERNEL(SCENE, MAXD)                                                                 \
+    extern "C" __global__ __launch_bounds__(64 * PT_WPW, PT_MIN_WG(SCENE, MAXD)) void pt_render_strict(PT_RENDER_ARGS) \
+    {                                                                                                       \
+        ptd::render_chunk<SCENE, MAXD, true>(P, imgs, jump, out, pixels, stats, lp);                       \
+    }
+#endif /* PT_CHAIN */
 #define PT_DEFINE_KERNELS(SCENE, MAXD)                                                                      \
     PT_DEFINE_LIGHT(SCENE, MAXD)                                                                            \
     extern "C" __global__ __launch_bounds__(64 * PT_WPW, PT_MIN_WG(SCENE, MAXD)) void pt_render_fast(PT_RENDER_ARGS) \

@@ -114,8 +114,21 @@ struct Generated
     bool bursts_all_leaf = false;     /* every burst's children are provably leaves */
 };
 
-/* rays: the module of pt_trace_rays (PT_RAYS), whose items are caller rays */
-Generated generate(const SceneImpl &s, int depth, bool rays = false);
+/* rays: the module of pt_trace_rays (PT_RAYS), whose items are caller rays;
+ * chain: the module of pt_trace_chains (PT_CHAIN), whose items draw from a
+ * chain's own engine state, one sample of each chain per launch */
+Generated generate(const SceneImpl &s, int depth, bool rays = false, bool chain = false);
+
+/* pt_trace_chains' step sequence.  Chain c has len[c] * spp steps; step t runs
+ * the chains with more than t steps.  order = the chain ids by descending
+ * length (ties by id), so those chains are the prefix order[0 .. items[t]);
+ * items has one count per step, max(len) * spp of them. */
+void chain_schedule(const int64_t *begin, int64_t nchains, int spp, std::vector<int32_t> &order,
+                    std::vector<int64_t> &items);
+/* pt_trace_chains' argument check, before any device is touched: throws
+ * Error(PT_ERR_ARG) naming the argument */
+void chain_validate(const pt_chain_params *p, const int32_t *pixels, const float *rays, const int64_t *begin,
+                    int64_t nchains, const uint64_t *states, const float *rgb_out);
 /* Query module for the boundary's query virtuals: pt_query_spans over object
  * `obj` (if >= 0) and pt_tex_eval of texture `tex` (if >= 0). */
 Generated generate_query(const SceneImpl &s, int obj, int tex);
@@ -137,7 +150,10 @@ ImageRec read_image(const std::string &path);
 void write_hdr(const std::string &path, const float *rgb, int w, int h);
 void write_bmp(const std::string &path, const float *rgb, int w, int h, int count);
 
-std::string device_library_source(); /* embedded pt_device.h */
+/* embedded pt_device.h; without its PT_CHAIN regions unless chain, so that the
+ * text -- and with it the code-object key -- of every other module kind is
+ * what it would be had the chained kind never been written */
+std::string device_library_source(bool chain = false);
 std::string device_user_object_source(); /* embedded pt_user_object.h (scenes with user objects) */
 std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scenes with multi-span user objects) */
 

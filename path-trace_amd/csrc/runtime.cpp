@@ -89,6 +89,15 @@ struct PtLaunchHost /* must match ptd::PtLaunch */
     int grab;
     const unsigned *list;
     unsigned *bail;
+    /* chained modules (PT_CHAIN) read on: other kernels take the fields above */
+    uint64_t *states;
+    const int *order;
+    const long long *begin;
+    int step, spp;
+    float *acc;
+    float *rgb;
+    uint64_t *state_after;
+    uint64_t *work;
 };
 
 template <class T>
@@ -169,6 +178,8 @@ struct DeviceState
     PinBuf<float> hout;
     DevBuf<int> pixels;
     DevBuf<uint64_t> stats;
+    DevBuf<uint64_t> chain;     /* pt_trace_chains' tables, sums, results and step counters (grow-only) */
+    PinBuf<uint64_t> hchain;    /* ... and their pinned staging */
     std::vector<PendingRender> pending; /* deferred timings (pt_render_device_timed) */
     ~DeviceState()
     {
@@ -179,6 +190,7 @@ struct DeviceState
             P.release(), imgs.release(), jump.release(), stage.release(), accum.release(), fb.release();
             out.release(), hpix.release(), hout.release();
             pixels.release(), stats.release();
+            chain.release(), hchain.release();
             for (auto &b : img_data) b.release();
             if (mod)
                 (void)hipModuleUnload(mod);
@@ -480,14 +492,14 @@ std::vector<uint64_t> jump_table()
     return t;
 }
 
-/* A scene's state on one device: the render module, or (rays) the ray-list
- * module of pt_trace_rays, each with its own buffers so that alternating calls
- * reload nothing. */
-constexpr int kRaysState = 1 << 16;
-DeviceState &device_state(SceneImpl &s, int device, const Generated &g, bool rays = false)
+/* A scene's state on one device: the render module, (rays) the ray-list
+ * module of pt_trace_rays or (chain) a chained module of pt_trace_chains, each
+ * with its own buffers so that alternating calls reload nothing. */
+constexpr int kRaysState = 1 << 16, kChainState = 1 << 17;
+DeviceState &device_state(SceneImpl &s, int device, const Generated &g, bool rays = false, bool chain = false)
 {
     HIPCHECK(hipSetDevice(device));
-    std::unique_ptr<DeviceState> &ds = s.devices[device | (rays ? kRaysState : 0)];
+    std::unique_ptr<DeviceState> &ds = s.devices[device | (rays ? kRaysState : 0) | (chain ? kChainState : 0)];
     if (!ds) {
         ds.reset(new DeviceState);
         ds->device = device;
@@ -502,9 +514,12 @@ DeviceState &device_state(SceneImpl &s, int device, const Generated &g, bool ray
             HIPCHECK(hipModuleUnload(ds->mod));
         ds->mod = nullptr;
         HIPCHECK(hipModuleLoadData(&ds->mod, code.data()));
-        HIPCHECK(hipModuleGetFunction(&ds->fast, ds->mod, "pt_render_fast"));
         HIPCHECK(hipModuleGetFunction(&ds->strict, ds->mod, "pt_render_strict"));
         HIPCHECK(hipModuleGetFunction(&ds->reduce, ds->mod, "pt_reduce"));
+        /* a chained module has the reference-order kernel alone (same launch bounds) */
+        ds->fast = ds->strict;
+        if (!chain)
+            HIPCHECK(hipModuleGetFunction(&ds->fast, ds->mod, "pt_render_fast"));
         int mt = 0;
         HIPCHECK(hipFuncGetAttribute(&mt, HIP_FUNC_ATTRIBUTE_MAX_THREADS_PER_BLOCK, ds->fast));
         if (mt < 64 || mt % 64)
@@ -721,11 +736,11 @@ struct Fnv
             bytes(v, n);
     }
 };
-std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays)
+std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays, bool chain = false)
 {
     if (const char *hdr = getenv("PT_DEVICE_HEADER")) /* experiment hook: the file may change under us */
         if (*hdr)
-            return std::make_shared<const Generated>(generate(s, depth, rays));
+            return std::make_shared<const Generated>(generate(s, depth, rays, chain));
     Fnv f;
     for (const ObjRec &o : s.objects) {
         f.add(o.kind), f.add(o.mat), f.add(o.a), f.add(o.b);
@@ -756,14 +771,14 @@ std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays)
     f.add(s.root), f.add(s.default_tex[0]), f.add(s.default_tex[1]);
     f.add(s.wg_per_cu), f.add(s.fast_spine), f.add(s.lane_walk), f.add(s.lane_scatter);
     f.add(s.lane_resume);
-    f.add(depth), f.add(rays);
+    f.add(depth), f.add(rays), f.add(chain);
     f.str(getenv("PT_DEVICE_DEFINES")), f.str(getenv("PT_JIT_OPTIONS"));
     auto it = s.gen_cache.find(f.h);
     if (it != s.gen_cache.end())
         return it->second;
     if (s.gen_cache.size() >= 16)
         s.gen_cache.clear();
-    auto g = std::make_shared<const Generated>(generate(s, depth, rays));
+    auto g = std::make_shared<const Generated>(generate(s, depth, rays, chain));
     s.gen_cache[f.h] = g;
     return g;
 }
@@ -1575,17 +1590,19 @@ int pt_scene_set_lane_resume(pt_scene *s, int on)
     });
 }
 
-const char *pt_scene_kernel_key(pt_scene *s, int depth)
+const char *pt_scene_module_key(pt_scene *s, int depth, int rays, int chain)
 {
     thread_local std::string k;
     try {
-        k = code_object_key(generate(S(s), depth));
+        k = code_object_key(generate(S(s), depth, rays != 0, chain != 0));
     } catch (std::exception &e) {
         set_error(e.what());
         k.clear();
     }
     return k.c_str();
 }
+
+const char *pt_scene_kernel_key(pt_scene *s, int depth) { return pt_scene_module_key(s, depth, 0, 0); }
 
 int pt_scene_reach_facts(pt_scene *s, int *kr_reach, int *bursts_all_leaf)
 {
@@ -1816,6 +1833,136 @@ int pt_trace_compile(pt_scene *s, int depth)
     return guard([&] {
         Generated g = generate(S(s), depth, true);
         code_object(g);
+        return PT_OK;
+    });
+}
+
+int pt_chain_compile(pt_scene *s, int depth, int rays)
+{
+    return guard([&] {
+        Generated g = generate(S(s), depth, rays != 0, true);
+        code_object(g);
+        return PT_OK;
+    });
+}
+
+/* One launch of the chained module per step (chain.cpp chain_schedule), all on
+ * the null stream, then one copy back and one synchronise.  The dependence of a
+ * chain's sample on the one before is the stream's order: launch t reads the
+ * engine states launch t - 1 wrote.  The device buffer, in 8-byte words:
+ *   [states nc][state_after n][rgb 3n floats][begin nc + 1][order nc ints]
+ *   [entries n ints | rays 7n floats][acc 3nc floats][work: one counter per step]
+ * -- the first three come back in one copy, states and the tables go up in one. */
+int pt_trace_chains(pt_scene *s, const pt_chain_params *p, const int32_t *pixels, const float *rays,
+                    const int64_t *begin, int64_t nchains, uint64_t *states, float *rgb_out, uint64_t *state_after,
+                    pt_render_stats *stats)
+{
+    return guard([&] {
+        chain_validate(p, pixels, rays, begin, nchains, states, rgb_out);
+        if (stats)
+            memset(stats, 0, sizeof(*stats));
+        std::vector<int32_t> order;
+        std::vector<int64_t> items;
+        chain_schedule(begin, nchains, p->spp, order, items);
+        const size_t steps = items.size();
+        if (steps == 0) /* every chain is empty: nothing runs, the states stay */
+            return PT_OK;
+        const size_t nc = (size_t)nchains, n = (size_t)begin[nchains];
+        auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+        const size_t o_after = nc, o_rgb = o_after + n, o_begin = o_rgb + words(12 * n), o_order = o_begin + nc + 1,
+                     o_entry = o_order + words(4 * nc), o_acc = o_entry + words(rays ? 28 * n : 4 * n),
+                     o_work = o_acc + words(12 * nc), total = o_work + steps;
+        SceneImpl &sc = S(s);
+        HIPCHECK(hipSetDevice(p->device));
+        std::shared_ptr<const Generated> gp = generated(sc, p->depth, rays != nullptr, true);
+        DeviceState &ds = device_state(sc, p->device, *gp, rays != nullptr, true);
+        ds.chain.ensure(total);
+        ds.hchain.ensure(o_acc);
+        uint64_t *const d = ds.chain.p, *const h = ds.hchain.p;
+        memcpy(h, states, 8 * nc);
+        memcpy(h + o_begin, begin, 8 * (nc + 1));
+        memcpy(h + o_order, order.data(), 4 * nc);
+        if (rays)
+            memcpy(h + o_entry, rays, 28 * n);
+        else
+            memcpy(h + o_entry, pixels, 4 * n);
+        hipStream_t stream = nullptr;
+        HIPCHECK(hipMemcpyAsync(d, h, 8 * nc, hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(d + o_begin, h + o_begin, 8 * (o_acc - o_begin), hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemsetAsync(d + o_work, 0, 8 * steps, stream));
+        HIPCHECK(hipMemsetAsync(ds.stats.p, 0, 40 * 8, stream));
+        PtLaunchHost lp;
+        memset(&lp, 0, sizeof lp);
+        lp.W = rays ? 1 : p->width, lp.H = rays ? 1 : p->height;
+        lp.sw = p->screen_w, lp.sh = p->screen_h, lp.dist = p->screen_dist;
+        lp.depth = p->depth;
+        lp.nsamp = 1; /* an item is one sample; its chain decides which (pt_device.h PT_CHAIN) */
+        lp.gw = lp.W;
+        lp.rays = rays ? (const float *)(d + o_entry) : nullptr;
+        lp.grab = 1;
+        lp.states = d, lp.state_after = d + o_after, lp.rgb = (float *)(d + o_rgb);
+        lp.begin = (const long long *)(d + o_begin), lp.order = (const int *)(d + o_order);
+        lp.acc = (float *)(d + o_acc);
+        lp.spp = p->spp;
+        const float *Pp = ds.P.p;
+        const PtImageDev *ip = ds.imgs.p;
+        const uint64_t *jp = ds.jump.p;
+        float *op = lp.rgb; /* the stage of the other kinds: a chained kernel writes lp.rgb itself */
+        const int *pp = rays ? nullptr : (const int *)(d + o_entry);
+        uint64_t *sp = ds.stats.p;
+        void *args[] = {&Pp, &ip, &jp, &op, &pp, &sp, &lp};
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        struct EvFree
+        {
+            hipEvent_t *e;
+            ~EvFree()
+            {
+                for (int k = 0; k < 2; k++)
+                    if (e[k])
+                        (void)hipEventDestroy(e[k]);
+            }
+        } evfree{ev};
+        if (stats) {
+            HIPCHECK(hipEventCreate(&ev[0]));
+            HIPCHECK(hipEventCreate(&ev[1]));
+            HIPCHECK(hipEventRecord(ev[0], stream));
+        }
+        const long long waves = (long long)ds.resident_blocks * ds.wpw;
+        uint64_t samples = 0;
+        for (size_t t = 0; t < steps; t++) {
+            /* as render_device: chunks small enough to give every resident wave a few */
+            int chunk = 64;
+            while (chunk > 1 && items[t] / chunk < 4 * waves) chunk /= 2;
+            const long long chunks = (items[t] + chunk - 1) / chunk;
+            const long long blocks = std::min<long long>(ds.resident_blocks, (chunks + ds.wpw - 1) / ds.wpw);
+            lp.n_items = items[t];
+            lp.chunk = chunk;
+            lp.step = (int)t;
+            lp.work = d + o_work + t;
+            HIPCHECK(hipModuleLaunchKernel(ds.strict, (unsigned)blocks, 1, 1, 64 * ds.wpw, 1, 1, 0, stream, args,
+                                           nullptr));
+            samples += (uint64_t)items[t];
+        }
+        if (stats)
+            HIPCHECK(hipEventRecord(ev[1], stream));
+        HIPCHECK(hipMemcpyAsync(h, d, 8 * o_begin, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        /* rgb of an entry is written with its last sample: every entry of every chain has one */
+        memcpy(states, h, 8 * nc);
+        if (state_after)
+            memcpy(state_after, h + o_after, 8 * n);
+        memcpy(rgb_out, h + o_rgb, 12 * n);
+        if (stats) {
+            float ms = 0;
+            HIPCHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            uint64_t c[40];
+            HIPCHECK(hipMemcpy(c, ds.stats.p, sizeof c, hipMemcpyDeviceToHost));
+            stats->kernel_ms = ms; /* first launch's start to last launch's end, the gaps between them included */
+            stats->launches = steps;
+            stats->samples = samples;
+            stats->queries = c[0] + c[1], stats->leaf_queries = c[1], stats->attempts = c[2], stats->rounds = c[3];
+            stats->shaded = c[4], stats->slow_queries = c[6], stats->dark_queries = c[7], stats->mid_queries = c[24];
+        }
         return PT_OK;
     });
 }

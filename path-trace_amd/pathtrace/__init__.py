@@ -18,8 +18,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import PT_ORDER_FAST, PT_ORDER_REFERENCE, PtError, RenderParams, RenderStats, TraceParams, load_hdr, \
-    load_png, write_bmp, write_hdr
+from ._lib import PT_ORDER_FAST, PT_ORDER_REFERENCE, ChainParams, PtError, RenderParams, RenderStats, TraceParams, \
+    load_hdr, load_png, write_bmp, write_hdr
 from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject, DeviceTexture, Difference, Image, ImageAlphaTexture, ImageSkyboxAlphaTexture,
                     ImageSkyboxTexture, ImageTexture, Intersection, LogTexture, Material, Matrix,
                     MirrorBallSkymapTexture, MultiplyTexture, Object, Plane, SphericalCoordinatesSkymapTexture,
@@ -27,7 +27,8 @@ from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject,
                     transform_material, transform_object, transform_texture, union_array)
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["DeviceScene", "render", "render_device", "prepare",
-                                                         "trace_rays", "lcg_state"]
+                                                         "trace_rays", "lcg_state", "trace_pixels_chained",
+                                                         "trace_rays_chained"]
 
 ORDERS = {"fast": PT_ORDER_FAST, "reference": PT_ORDER_REFERENCE,
           "strict": PT_ORDER_REFERENCE,
@@ -211,6 +212,19 @@ class DeviceScene:
         """Compile pt_trace_rays' module for this scene and depth (no device)."""
         _lib.check(_lib.lib().pt_trace_compile(self._h, depth))
 
+    def compile_chain(self, depth: int, rays: bool = False) -> None:
+        """Compile pt_trace_chains' module for this scene and depth -- the pixel
+        kind, or with rays the ray kind (no device)."""
+        _lib.check(_lib.lib().pt_chain_compile(self._h, depth, 1 if rays else 0))
+
+    def module_key(self, depth: int, rays: bool = False, chain: bool = False) -> str:
+        """kernel_key for any of the scene's module kinds (pt_scene_module_key):
+        the ray-list module, the chained module, the chained module for rays."""
+        k = _lib.lib().pt_scene_module_key(self._h, depth, 1 if rays else 0, 1 if chain else 0).decode()
+        if not k:
+            raise PtError(_lib.lib().pt_last_error().decode())
+        return k
+
     def compile(self, depth: int) -> str:
         _lib.check(_lib.lib().pt_scene_compile(self._h, depth))
         return _lib.lib().pt_scene_kernel_key(self._h, depth).decode()
@@ -278,6 +292,52 @@ def trace_rays(scene, rays, depth: int, spp: int = 1, seed: int = 0x5EED, order=
     _lib.check(_lib.lib().pt_trace_rays(ds.handle, ctypes.byref(tp), r.ctypes.data, len(r), out.ctypes.data,
                                         ctypes.byref(st)))
     return (out, st.as_dict()) if stats else out
+
+
+def _trace_chains(scene, pixels, rays, begin, states, width, height, spp, depth, screen, device, stats):
+    ds = scene if isinstance(scene, DeviceScene) else DeviceScene(scene)
+    begin = np.ascontiguousarray(begin, dtype=np.int64)
+    final = np.array(states, dtype=np.uint64, ndmin=1)  # a copy: in the initial states, out the final ones
+    entries = pixels if rays is None else rays
+    if len(begin) != len(final) + 1:
+        raise ValueError("begin needs one offset per chain and the entry count")
+    if len(begin) and int(begin[-1]) != len(entries):
+        raise ValueError("begin[-1] must be the number of entries")
+    sw, sh, dist = screen if screen is not None else (float(width), float(height), float(2 * min(width, height)))
+    p = ChainParams()
+    p.width, p.height, p.spp, p.depth = int(width), int(height), int(spp), int(depth)
+    p.screen_w, p.screen_h, p.screen_dist, p.device = float(sw), float(sh), float(dist), int(device)
+    colour = np.zeros((len(entries), 3), dtype=np.float32)
+    after = np.zeros(len(entries), dtype=np.uint64)
+    st = RenderStats()
+    _lib.check(_lib.lib().pt_trace_chains(ds.handle, ctypes.byref(p), None if pixels is None else pixels.ctypes.data,
+                                          None if rays is None else rays.ctypes.data, begin.ctypes.data, len(final),
+                                          final.ctypes.data, colour.ctypes.data, after.ctypes.data,
+                                          ctypes.byref(st) if stats else None))
+    return (colour, after, final, st.as_dict()) if stats else (colour, after, final)
+
+
+def trace_pixels_chained(scene, entries, begin, states, width, height, spp, depth, screen=None, device=0,
+                         stats: bool = False):
+    """tracePixel<T> (include/path-trace.h:187-201) pixel after pixel on the
+    caller's DefaultRandomEngine states, as a program that owns one engine runs
+    it (pt_trace_chains): chain c is the pixel indices entries[begin[c]:begin[c + 1]]
+    (py * width + px), traced in order with ONE engine that starts at states[c]
+    (lcg_state(seed) after seed()).  Chains run side by side.  Returns
+    (colour[n, 3], state_after[n], final_state[nchains]): the reference's bits."""
+    pix = np.ascontiguousarray(entries, dtype=np.int32).reshape(-1)
+    return _trace_chains(scene, pix, None, begin, states, width, height, spp, depth, screen, device, stats)
+
+
+def trace_rays_chained(scene, entries, begin, states, spp, depth, device=0, stats: bool = False):
+    """The same for traceRay<T>: entries are rays (n x 7 float32: origin,
+    direction, strength; n x 6 takes strength 1), each traced spp times on its
+    chain's engine and averaged (the sample loop of include/path-trace.h:178-183)."""
+    r = np.asarray(entries, dtype=np.float32)
+    if r.ndim == 2 and r.shape[1] == 6:
+        r = np.concatenate([r, np.ones((len(r), 1), dtype=np.float32)], axis=1)
+    r = np.ascontiguousarray(r.reshape(-1, 7))
+    return _trace_chains(scene, None, r, begin, states, 1, 1, spp, depth, None, device, stats)
 
 
 def lcg_state(seed: int) -> int:

@@ -42,6 +42,12 @@ class TraceParams(ctypes.Structure):
                 ("ray_begin", ctypes.c_int64)]
 
 
+class ChainParams(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("spp", ctypes.c_int), ("depth", ctypes.c_int),
+                ("screen_w", ctypes.c_float), ("screen_h", ctypes.c_float), ("screen_dist", ctypes.c_float),
+                ("device", ctypes.c_int)]
+
+
 class RenderStats(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double), ("reduce_ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("samples", ctypes.c_uint64), ("queries", ctypes.c_uint64), ("leaf_queries", ctypes.c_uint64),
@@ -107,6 +113,9 @@ SIGNATURES = {
                                 ctypes.POINTER(RenderStats)]),
     "pt_trace_rays": (_I, [_P, ctypes.POINTER(TraceParams), _P, ctypes.c_int64, _P, ctypes.POINTER(RenderStats)]),
     "pt_trace_compile": (_I, [_P, _I]),
+    "pt_trace_chains": (_I, [_P, ctypes.POINTER(ChainParams), _P, _P, _P, ctypes.c_int64, _P, _P, _P,
+                             ctypes.POINTER(RenderStats)]),
+    "pt_chain_compile": (_I, [_P, _I, _I]),
     "pt_prepare": (_I, [_P, ctypes.POINTER(RenderParams)]),
     "pt_scene_compile": (_I, [_P, _I]),
     "pt_scene_set_occupancy": (_I, [_P, _I]),
@@ -116,6 +125,7 @@ SIGNATURES = {
     "pt_scene_set_lane_scatter": (_I, [_P, _I]),
     "pt_scene_set_lane_resume": (_I, [_P, _I]),
     "pt_scene_kernel_key": (ctypes.c_char_p, [_P, _I]),
+    "pt_scene_module_key": (ctypes.c_char_p, [_P, _I, _I, _I]),
     "pt_scene_reach_facts": (_I, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "pt_selftest_math": (_I, [_I, ctypes.c_uint64, ctypes.c_uint64, _P]),
     "pt_selftest_libm": (_I, [_I, _P, ctypes.c_int64, _P]),

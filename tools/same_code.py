@@ -19,6 +19,11 @@ ranges ("0-8,41"; the product's configurations come first, in
 scenes.CONFIGS' order).  --scratch keeps the two caches in DIR, so a second
 run compiles only what changed; the default is a temporary directory.
 
+Only chained modules (PT_CHAIN) are generated from the header's PT_CHAIN
+regions; every other kind gets the header without them (csrc/devsrc.cpp).  An
+old header from before that kind cannot build a chained module: those jobs
+are compiled on the new side alone and listed as "new kind".
+
 Bytes and line counts only: which instructions a kernel uses is not looked at."""
 import collections
 import hashlib
@@ -54,17 +59,41 @@ def _llvm(tool: str) -> str:
     return os.path.join(rocm, "llvm", "bin", tool)
 
 
+def _without_chain(text: str) -> str:
+    """csrc/devsrc.cpp without_chain: the header as every module kind but the chained one gets it"""
+    out, skip = [], False
+    for ln in text.splitlines(keepends=True):
+        if ln.rstrip("\n") == "#ifdef PT_CHAIN":
+            skip = True
+        if not skip:
+            out.append(ln)
+        elif ln.rstrip("\n") == "#endif /* PT_CHAIN */":
+            skip = False
+    return "".join(out)
+
+
 def _modules(cache: str, header: str, since: float) -> dict:
     """the code objects this run used (the runtime touches the ones it serves), by their generated
     source without the header's text"""
     text = open(header).read()
+    plain = _without_chain(text)
     out = {}
     for f in sorted(os.listdir(cache)):
         hsaco = os.path.join(cache, f[:-4] + ".hsaco")
         if f.endswith(".hip") and os.path.exists(hsaco) and os.path.getmtime(hsaco) >= since:
             src = open(os.path.join(cache, f)).read()
-            out[src.replace(text, "<pt_device.h>", 1)] = f[:-4]
+            out[src.replace(text if text in src else plain, "<pt_device.h>", 1)] = f[:-4]
     return out
+
+
+def _chain_jobs(entry) -> set:
+    """the indices of tests/precompile_chain.py's jobs in _jobs(): they precede the inside-zero tail"""
+    try:
+        import precompile_chain
+    except ImportError:
+        return set()
+    end = len(entry._jobs()) - len(entry._inside_zero_jobs())
+    return set(range(end - len(precompile_chain.test_jobs()), end))
 
 
 def _section(hsaco: str, name: str) -> bytes:
@@ -145,6 +174,7 @@ def main(argv) -> int:
     if scratch is None:
         tmp = tempfile.TemporaryDirectory(prefix="same_code_")
         scratch = tmp.name
+    new_only = set() if "PT_CHAIN" in open(old_header).read() else _chain_jobs(entry)
     caches = {side: os.path.join(scratch, side) for side in ("old", "new")}
     for c in caches.values():
         os.makedirs(c, exist_ok=True)
@@ -156,6 +186,8 @@ def main(argv) -> int:
             print(open(p.log).read()[-4000:])
     for k in picked:
         for side in ("old", "new"):
+            if side == "old" and k in new_only:
+                continue
             env = dict(os.environ, PT_JIT_CACHE=caches[side])
             env.pop("PT_DEVICE_HEADER", None)
             if side == "old":
@@ -180,7 +212,9 @@ def main(argv) -> int:
     old, new = _modules(caches["old"], old_header, start), _modules(caches["new"], HEADER, start)
     classes = collections.Counter()
     for residual in sorted(set(old) | set(new), key=_label):
-        if residual not in old or residual not in new:
+        if residual not in old and re.search(r"^#define PT_CHAIN 1$", residual.split("<pt_device.h>")[0], re.M):
+            res = "new kind"
+        elif residual not in old or residual not in new:
             res = "UNPAIRED (only in the %s cache)" % ("old" if residual in old else "new")
         else:
             res = _compare(os.path.join(caches["old"], old[residual] + ".hsaco"),
@@ -189,7 +223,7 @@ def main(argv) -> int:
         print("%s -> %s  %s: %s" % (old.get(residual, "-" * 16), new.get(residual, "-" * 16), _label(residual), res))
     print("%d jobs, %d modules: %s" % (len(picked), sum(classes.values()),
                                        ", ".join("%d %s" % (v, k) for k, v in sorted(classes.items()))))
-    return 0 if set(classes) <= {"identical"} else 1
+    return 0 if set(classes) <= {"identical", "new kind"} else 1
 
 
 if __name__ == "__main__":
