@@ -1463,6 +1463,34 @@ public:
         return out;
     }
 
+    /* Converged rendering (pt_render_converge): every pixel -- or entry of
+     * pixels -- is sampled in rounds of minSamples, 2 minSamples, ... until the
+     * standard error of its mean r + g + b is within max(absTol, relTol |mean|)
+     * or st.sampleCount (the cap, a multiple of 32) is reached.  Returns the
+     * colours; spp / err (optional) receive each entry's sample count and
+     * standard error, info the rounds, traced samples and capped entries.  An
+     * entry with n samples holds what render() gives it with sampleCount = n. */
+    std::vector<Color> renderConverged(const Settings &st, float relTol, float absTol = 0, int minSamples = 64,
+                                       std::vector<int32_t> *spp = nullptr, std::vector<float> *err = nullptr,
+                                       pt_converge_params *info = nullptr, const int32_t *pixels = nullptr,
+                                       int64_t npixels = 0, pt_render_stats *stats = nullptr) const
+    {
+        pt_render_params p = params(st, pixels, npixels);
+        pt_converge_params cp = {};
+        cp.min_spp = minSamples, cp.rel_tol = relTol, cp.abs_tol = absTol;
+        const size_t n = (size_t)(pixels ? npixels : (int64_t)st.width * st.height);
+        std::vector<Color> out(n);
+        if (spp)
+            spp->assign(n, 0);
+        if (err)
+            err->assign(n, 0.0f);
+        ptCheck(pt_render_converge(s_, &p, &cp, reinterpret_cast<float *>(out.data()), spp ? spp->data() : nullptr,
+                                   err ? err->data() : nullptr, stats));
+        if (info)
+            *info = cp;
+        return out;
+    }
+
     /* Compile / upload everything a render with these settings needs. */
     void prepare(const Settings &st) const
     {

@@ -300,6 +300,40 @@ typedef struct pt_adaptive_params {
 int pt_render_adaptive(pt_scene *s, const pt_render_params *p, pt_adaptive_params *ap, float *rgb_out,
                        pt_render_stats *stats);
 
+/* Converged rendering, no reference counterpart: every entry (a pixel of
+ * p->pixels, or of the whole frame) is sampled until the standard error of its
+ * mean is within a tolerance, instead of p->spp times.  Rounds: round 0 traces
+ * samples [0, min_spp) of every entry, round r + 1 samples [n_r, min(2 n_r,
+ * p->spp)) of the entries that have not stopped; the call ends when none is
+ * left.  At the end of a round an entry with n = 32 m samples has m block sums
+ * B_j (the fast order's 32-sample blocks); with y_j = (B_j.r + B_j.g) + B_j.b
+ * in f32 and s1 = sum y_j, s2 = sum y_j^2 in f64 (block order),
+ *     e2 = max(s2 - s1 s1 / m, 0) / (m (m - 1)),
+ *     t  = max(32 abs_tol, rel_tol |s1 / m|),
+ * it stops iff e2 <= t t or n == p->spp; an entry whose s1 or s2 is not finite
+ * stops at once with err = NaN.  A stopped entry holds rgb = its sums / n --
+ * bit for bit what pt_render gives that pixel with spp = n --, spp = n and
+ * err = sqrt(e2) / 32: the standard error of the mean per-sample r + g + b,
+ * estimated from the spread of the block means (batch means).
+ * p->spp is the cap (a multiple of 32), p->order PT_ORDER_FAST, p->sample_begin
+ * and p->sum_only 0; pixels and grid_width as in pt_render.  Outputs are per
+ * entry, compact (3 floats, 1 int, 1 float at entry k); spp_out and err_out
+ * may be NULL.  stats sum over the rounds (reduce_ms: the moments, decision
+ * and compaction kernels).  Every argument is checked before a device is
+ * touched: PT_ERR_ARG names the argument in pt_last_error(). */
+typedef struct pt_converge_params {
+    int min_spp;                   /* first round; a multiple of 32, >= 64, <= p->spp           */
+    float rel_tol, abs_tol;        /* >= 0, not NaN                                             */
+    int rounds;                    /* out                                                       */
+    int64_t samples;               /* out: samples traced                                       */
+    int64_t capped;                /* out: entries that stopped only because n reached p->spp   */
+} pt_converge_params;
+int pt_render_converge(pt_scene *s, const pt_render_params *p, pt_converge_params *cp, float *rgb_out,
+                       int32_t *spp_out, float *err_out, pt_render_stats *stats);
+/* JIT-compile (or fetch from the code-object cache) pt_render_converge's
+ * scene-independent module without touching a GPU. */
+int pt_converge_compile(void);
+
 /* traceRay<T>(const Ray &ray, SpanIterator &, int depth, T &engine, float
  * strength) of include/path-trace.h:58-165 for a batch of caller rays, in one
  * device launch.  rays = n records of 7 floats: origin xyz, direction xyz

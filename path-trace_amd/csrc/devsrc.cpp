@@ -71,4 +71,11 @@ std::string device_user_object_n_source()
         ;
     return src;
 }
+std::string device_converge_source()
+{
+    static const char src[] =
+#include "pt_converge_src.inc"
+        ;
+    return src;
+}
 } // namespace pt

@@ -156,6 +156,7 @@ void write_bmp(const std::string &path, const float *rgb, int w, int h, int coun
 std::string device_library_source(bool chain = false);
 std::string device_user_object_source(); /* embedded pt_user_object.h (scenes with user objects) */
 std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scenes with multi-span user objects) */
+std::string device_converge_source(); /* embedded pt_converge.h (pt_render_converge's scene-independent module) */
 
 } // namespace pt
 

@@ -155,6 +155,27 @@ struct PendingRender
     int n_spheres = 0, n_planes = 0;
 };
 
+/* pt_render_converge's module (pt_converge.h) and per-entry state on one device */
+struct ConvergeDev
+{
+    hipModule_t mod = nullptr;
+    hipFunction_t reduce = nullptr, scan = nullptr, scatter = nullptr;
+    DevBuf<float> acc, rgb, err;
+    DevBuf<double> mom;
+    DevBuf<int> blocks, spp, keep, list[4]; /* list: two (pixel, home) pairs, written in turn */
+    DevBuf<unsigned> wg;                    /* per-workgroup keeps, capped counts and offsets */
+    DevBuf<uint64_t> word;
+    void release()
+    {
+        acc.release(), rgb.release(), err.release(), mom.release(), blocks.release(), spp.release();
+        keep.release(), wg.release(), word.release();
+        for (auto &l : list) l.release();
+        if (mod)
+            (void)hipModuleUnload(mod);
+        mod = nullptr;
+    }
+};
+
 struct DeviceState
 {
     int device = 0;
@@ -180,6 +201,7 @@ struct DeviceState
     DevBuf<uint64_t> stats;
     DevBuf<uint64_t> chain;     /* pt_trace_chains' tables, sums, results and step counters (grow-only) */
     PinBuf<uint64_t> hchain;    /* ... and their pinned staging */
+    ConvergeDev conv;
     std::vector<PendingRender> pending; /* deferred timings (pt_render_device_timed) */
     ~DeviceState()
     {
@@ -191,6 +213,7 @@ struct DeviceState
             out.release(), hpix.release(), hout.release();
             pixels.release(), stats.release();
             chain.release(), hchain.release();
+            conv.release();
             for (auto &b : img_data) b.release();
             if (mod)
                 (void)hipModuleUnload(mod);
@@ -878,6 +901,130 @@ void collect_timings(DeviceState &ds, pt_render_stats *st)
  * its frame position, fb[3 * pixels[k]]) */
 constexpr size_t kMaxPending = 1024; /* deferred renders a device keeps before a collect is required */
 
+struct EvGuard /* events of a render that throws before it is recorded */
+{
+    PendingRender &pr;
+    bool kept = false;
+    ~EvGuard()
+    {
+        if (!kept)
+            for (auto e : pr.evs) (void)hipEventDestroy(e);
+    }
+};
+void record_event(PendingRender &pr, hipStream_t stream)
+{
+    hipEvent_t e;
+    HIPCHECK(hipEventCreate(&e));
+    pr.evs.push_back(e);
+    HIPCHECK(hipEventRecord(e, stream));
+}
+
+/* What the passes of one call share (render_device, pt_render_converge) */
+struct PassLaunch
+{
+    SceneImpl &s;
+    DeviceState &ds;
+    hipStream_t stream;
+    bool timed;
+    PendingRender &pr;
+    const float *rays;
+    int64_t ray0;
+};
+
+/* One render pass: samples p->sample_begin + s0 .. + nsamp - 1 of the npix
+ * slots of the device-resident list dpix (null: slot = pixel) into ds.stage.
+ * Returns pt_reduce's mode for the layout the launch staged. */
+int launch_pass(const PassLaunch &L, const pt_render_params *p, const int *dpix, long long npix, int s0, int nsamp)
+{
+    SceneImpl &s = L.s;
+    DeviceState &ds = L.ds;
+    hipStream_t stream = L.stream;
+    PendingRender &pr = L.pr;
+    hipFunction_t fn = p->order == PT_ORDER_REFERENCE ? ds.strict : ds.fast;
+    int reduce_mode = 0;
+    long long n_items = npix * nsamp;
+    /* 64 items per dequeue: every lane of the chunk's camera phase busy
+     * (same-box A/B: C5 2430 -> 4490 Msamples/s, C3 +0.5 %; round 1: C3
+     * 16 -> 32 +2.7 %); a launch too small to give every resident wave a
+     * few chunks takes fewer, so one wave does not trace many samples of
+     * one expensive pixel while others idle */
+    const long long waves = (long long)ds.resident_blocks * ds.wpw;
+    static const int chunk_max = [] {
+        const char *env = getenv("PT_CHUNK_MAX"); /* experiment hook (1..64) */
+        if (!env || !*env)
+            return 64;
+        fprintf(stderr, "pt: experiment hook PT_CHUNK_MAX=%s active\n", env);
+        return std::max(1, std::min(64, atoi(env)));
+    }();
+    int chunk = chunk_max;
+    /* slot-major launches of few samples per pixel (a multi-GPU rank's
+     * share: C3 at 8 ranks = 128 per pixel) take 32-sample chunks: a
+     * chunk is then half as many samples of one expensive pixel, which
+     * shortens the launch's tail (same-box A/B at 128 spp: 147.2 -> 153.3
+     * Msamples/s; at 256 spp 64 stays ahead, 156.0 vs 153.2) */
+    if (nsamp > 64 && nsamp <= 128)
+        chunk = std::min(chunk, 32);
+    while (chunk > 1 && n_items / chunk < 4 * waves) chunk /= 2;
+    long long chunks = (n_items + chunk - 1) / chunk;
+    const int wpw = ds.wpw;
+    long long blocks = std::min<long long>(ds.resident_blocks, (chunks + wpw - 1) / wpw);
+    long long c0 = 0;
+    PtLaunchHost lp;
+    memset(&lp, 0, sizeof lp);
+    lp.seed = p->seed;
+    lp.n_items = n_items;
+    lp.chunk0 = c0;
+    lp.W = p->width, lp.H = p->height;
+    lp.sw = p->screen_w, lp.sh = p->screen_h, lp.dist = p->screen_dist;
+    lp.depth = p->depth;
+    lp.nsamp = nsamp;
+    lp.s0 = p->sample_begin + s0;
+    lp.gw = p->grid_width > 0 ? p->grid_width : p->width;
+    lp.chunk = chunk;
+    /* sample-major item order for launches of up to 64 samples per slot
+     * (pt_device.h item_slot) */
+    lp.sample_major = nsamp <= 64 ? 1 : 0;
+    if (lp.sample_major)
+        lp.perm = slot_permutation(npix);
+    /* one staged partial per 32-sample block when a chunk is a block */
+    lp.block_sums =
+        (block_staging(p) && !lp.sample_major && (chunk == 32 || chunk == 64) && nsamp % chunk == 0) ? 1 : 0;
+    lp.rays = L.rays;
+    lp.ray0 = L.ray0;
+    lp.grab = grab_chunks(s);
+    /* split launch (lane-walk modules, fast order): the light kernel
+     * over every chunk, then the full kernel over the ones it left */
+    const bool split = ds.light && fn == ds.fast && s.split && split_launches() && chunks < (1ll << 32);
+    reduce_mode = p->order == PT_ORDER_REFERENCE ? 0 : lp.block_sums ? 2 : 1;
+    ds.stage.ensure((size_t)(lp.block_sums ? npix * (nsamp / 32) * 3 : npix * nsamp * 3));
+    const float *Pp = ds.P.p;
+    const PtImageDev *ip = ds.imgs.p;
+    const uint64_t *jp = ds.jump.p;
+    float *op = ds.stage.p;
+    const int *pp = dpix;
+    uint64_t *sp = ds.stats.p; /* counters + the persistent chunk counter (stats[15]) */
+    HIPCHECK(hipMemsetAsync(ds.stats.p + 15, 0, 8, stream));
+    void *args[] = {&Pp, &ip, &jp, &op, &pp, &sp, &lp};
+    int e0 = (int)pr.evs.size();
+    if (L.timed)
+        record_event(pr, stream);
+    if (split) {
+        ds.bail.ensure((size_t)chunks);
+        HIPCHECK(hipMemsetAsync(ds.stats.p + 35, 0, 16, stream)); /* list length, its queue */
+        lp.bail = ds.bail.p;
+        const long long lblocks = std::min<long long>(ds.light_blocks, (chunks + wpw - 1) / wpw);
+        HIPCHECK(hipModuleLaunchKernel(ds.light, (unsigned)lblocks, 1, 1, 64 * wpw, 1, 1, 0, stream, args, nullptr));
+        lp.bail = nullptr;
+        lp.list = ds.bail.p;
+    }
+    HIPCHECK(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 64 * wpw, 1, 1, 0, stream, args, nullptr));
+    if (L.timed) {
+        record_event(pr, stream);
+        pr.spans.push_back({e0, e0 + 1});
+    }
+    return reduce_mode;
+}
+
 /* rays (device memory, 7 floats per slot): the ray-list module of
  * pt_trace_rays renders slot k = ray k instead of a camera pixel */
 void render_device(SceneImpl &s, const pt_render_params *p, float *fb, hipStream_t stream, pt_render_stats *st,
@@ -915,111 +1062,14 @@ void render_device(SceneImpl &s, const pt_render_params *p, float *fb, hipStream
     /* the counters restart with the first recorded render */
     if (!timed || ds.pending.empty())
         HIPCHECK(hipMemsetAsync(ds.stats.p, 0, 40 * 8, stream));
-    hipFunction_t fn = p->order == PT_ORDER_REFERENCE ? ds.strict : ds.fast;
     PendingRender pr;
     pr.n_spheres = g.n_spheres, pr.n_planes = g.n_planes;
-    struct EvGuard /* events of a render that throws before it is recorded */
-    {
-        PendingRender &pr;
-        bool kept = false;
-        ~EvGuard()
-        {
-            if (!kept)
-                for (auto e : pr.evs) (void)hipEventDestroy(e);
-        }
-    } eg{pr};
-    auto event = [&]() {
-        hipEvent_t e;
-        HIPCHECK(hipEventCreate(&e));
-        pr.evs.push_back(e);
-        HIPCHECK(hipEventRecord(e, stream));
-    };
+    EvGuard eg{pr};
+    const PassLaunch L{s, ds, stream, timed, pr, rays, ray0};
     for (int s0 = 0; s0 < p->spp; s0 += (int)per_pass) {
-        int reduce_mode = 0;
         int nsamp = (int)std::min<long long>(per_pass, p->spp - s0);
         long long n_items = npix * nsamp;
-        /* 64 items per dequeue: every lane of the chunk's camera phase busy
-         * (same-box A/B: C5 2430 -> 4490 Msamples/s, C3 +0.5 %; round 1: C3
-         * 16 -> 32 +2.7 %); a launch too small to give every resident wave a
-         * few chunks takes fewer, so one wave does not trace many samples of
-         * one expensive pixel while others idle */
-        const long long waves = (long long)ds.resident_blocks * ds.wpw;
-        static const int chunk_max = [] {
-            const char *env = getenv("PT_CHUNK_MAX"); /* experiment hook (1..64) */
-            if (!env || !*env)
-                return 64;
-            fprintf(stderr, "pt: experiment hook PT_CHUNK_MAX=%s active\n", env);
-            return std::max(1, std::min(64, atoi(env)));
-        }();
-        int chunk = chunk_max;
-        /* slot-major launches of few samples per pixel (a multi-GPU rank's
-         * share: C3 at 8 ranks = 128 per pixel) take 32-sample chunks: a
-         * chunk is then half as many samples of one expensive pixel, which
-         * shortens the launch's tail (same-box A/B at 128 spp: 147.2 -> 153.3
-         * Msamples/s; at 256 spp 64 stays ahead, 156.0 vs 153.2) */
-        if (nsamp > 64 && nsamp <= 128)
-            chunk = std::min(chunk, 32);
-        while (chunk > 1 && n_items / chunk < 4 * waves) chunk /= 2;
-        long long chunks = (n_items + chunk - 1) / chunk;
-        const int wpw = ds.wpw;
-        {
-            long long blocks = std::min<long long>(ds.resident_blocks, (chunks + wpw - 1) / wpw);
-            long long c0 = 0;
-            PtLaunchHost lp;
-            memset(&lp, 0, sizeof lp);
-            lp.seed = p->seed;
-            lp.n_items = n_items;
-            lp.chunk0 = c0;
-            lp.W = p->width, lp.H = p->height;
-            lp.sw = p->screen_w, lp.sh = p->screen_h, lp.dist = p->screen_dist;
-            lp.depth = p->depth;
-            lp.nsamp = nsamp;
-            lp.s0 = p->sample_begin + s0;
-            lp.gw = p->grid_width > 0 ? p->grid_width : p->width;
-            lp.chunk = chunk;
-            /* sample-major item order for launches of up to 64 samples per slot
-             * (pt_device.h item_slot) */
-            lp.sample_major = nsamp <= 64 ? 1 : 0;
-            if (lp.sample_major)
-                lp.perm = slot_permutation(npix);
-            /* one staged partial per 32-sample block when a chunk is a block */
-            lp.block_sums =
-                (block_staging(p) && !lp.sample_major && (chunk == 32 || chunk == 64) && nsamp % chunk == 0) ? 1 : 0;
-            lp.rays = rays;
-            lp.ray0 = ray0;
-            lp.grab = grab_chunks(s);
-            /* split launch (lane-walk modules, fast order): the light kernel
-             * over every chunk, then the full kernel over the ones it left */
-            const bool split = ds.light && fn == ds.fast && s.split && split_launches() && chunks < (1ll << 32);
-            reduce_mode = p->order == PT_ORDER_REFERENCE ? 0 : lp.block_sums ? 2 : 1;
-            ds.stage.ensure((size_t)(lp.block_sums ? npix * (nsamp / 32) * 3 : npix * nsamp * 3));
-            const float *Pp = ds.P.p;
-            const PtImageDev *ip = ds.imgs.p;
-            const uint64_t *jp = ds.jump.p;
-            float *op = ds.stage.p;
-            const int *pp = dpix;
-            uint64_t *sp = ds.stats.p; /* counters + the persistent chunk counter (stats[15]) */
-            HIPCHECK(hipMemsetAsync(ds.stats.p + 15, 0, 8, stream));
-            void *args[] = {&Pp, &ip, &jp, &op, &pp, &sp, &lp};
-            int e0 = (int)pr.evs.size();
-            if (timed)
-                event();
-            if (split) {
-                ds.bail.ensure((size_t)chunks);
-                HIPCHECK(hipMemsetAsync(ds.stats.p + 35, 0, 16, stream)); /* list length, its queue */
-                lp.bail = ds.bail.p;
-                const long long lblocks = std::min<long long>(ds.light_blocks, (chunks + wpw - 1) / wpw);
-                HIPCHECK(hipModuleLaunchKernel(ds.light, (unsigned)lblocks, 1, 1, 64 * wpw, 1, 1, 0, stream, args,
-                                               nullptr));
-                lp.bail = nullptr;
-                lp.list = ds.bail.p;
-            }
-            HIPCHECK(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 64 * wpw, 1, 1, 0, stream, args, nullptr));
-            if (timed) {
-                event();
-                pr.spans.push_back({e0, e0 + 1});
-            }
-        }
+        int reduce_mode = launch_pass(L, p, dpix, npix, s0, nsamp);
         {
             const float *in = ds.stage.p;
             float *acc = ds.accum.p;
@@ -1031,10 +1081,10 @@ void render_device(SceneImpl &s, const pt_render_params *p, float *fb, hipStream
             unsigned blocks = (unsigned)((npix + 255) / 256);
             int e0 = (int)pr.evs.size();
             if (timed)
-                event();
+                record_event(pr, stream);
             HIPCHECK(hipModuleLaunchKernel(ds.reduce, blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
             if (timed) {
-                event();
+                record_event(pr, stream);
                 pr.rspans.push_back({e0, e0 + 1});
             }
         }
@@ -1045,6 +1095,190 @@ void render_device(SceneImpl &s, const pt_render_params *p, float *fb, hipStream
     eg.kept = true;
     ds.pending.push_back(std::move(pr));
     if (tm == Timing::Sync)
+        collect_timings(ds, st);
+}
+
+/* ------------------------------------------------- converged rendering -- */
+struct PtConvergeHost /* must match pt_converge.h PtConverge */
+{
+    const float *stage;
+    const int *pix;
+    const int *home;
+    long long n;
+    int nsamp, mode, first, last, cap;
+    float rel_tol, abs_tol;
+    float *acc;
+    double *mom;
+    int *blocks;
+    float *rgb;
+    int *spp;
+    float *err;
+    int *keep;
+    unsigned *wg_keep, *wg_capped, *wg_off;
+    uint64_t *word;
+    int nwg;
+    int *pix_next, *home_next;
+};
+
+/* pt_render_converge's scene-independent module (device/pt_converge.h), with
+ * the scene modules' compiler options */
+Generated converge_generated()
+{
+    Generated g;
+    g.source = device_converge_source();
+    g.key = "converge";
+    return g;
+}
+
+/* pt_render_converge's argument check, before any device is touched */
+void converge_validate(const pt_render_params *p, const pt_converge_params *cp, const float *rgb_out)
+{
+    if (!p)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p is null");
+    if (!cp)
+        throw Error(PT_ERR_ARG, "pt_render_converge: cp is null");
+    if (!rgb_out)
+        throw Error(PT_ERR_ARG, "pt_render_converge: rgb_out is null");
+    validate(p);
+    if (p->pixels && p->npixels < 0)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p->npixels is negative");
+    if (p->order != PT_ORDER_FAST)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p->order must be PT_ORDER_FAST");
+    if (p->sample_begin != 0)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p->sample_begin must be 0");
+    if (p->sum_only != 0)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p->sum_only must be 0");
+    if (p->spp % 32 != 0)
+        throw Error(PT_ERR_ARG, "pt_render_converge: p->spp (the cap) must be a multiple of 32");
+    if (cp->min_spp < 64 || cp->min_spp % 32 != 0 || cp->min_spp > p->spp)
+        throw Error(PT_ERR_ARG, "pt_render_converge: cp->min_spp must be a multiple of 32, >= 64 and <= p->spp");
+    if (!(cp->rel_tol >= 0.0f))
+        throw Error(PT_ERR_ARG, "pt_render_converge: cp->rel_tol must be >= 0 and not NaN");
+    if (!(cp->abs_tol >= 0.0f))
+        throw Error(PT_ERR_ARG, "pt_render_converge: cp->abs_tol must be >= 0 and not NaN");
+}
+
+void render_converge(SceneImpl &s, const pt_render_params *p, pt_converge_params *cp, float *rgb_out,
+                     int32_t *spp_out, float *err_out, pt_render_stats *st)
+{
+    converge_validate(p, cp, rgb_out);
+    cp->rounds = 0, cp->samples = 0, cp->capped = 0;
+    if (st)
+        memset(st, 0, sizeof(*st));
+    const long long n0 = p->pixels ? (long long)p->npixels : (long long)p->width * p->height;
+    if (n0 == 0)
+        return;
+    const Generated cg = converge_generated();
+    const std::vector<char> &code = code_object(cg);
+    /* the first round sizes the render module's buffers */
+    pt_render_params q = *p;
+    q.spp = cp->min_spp;
+    std::shared_ptr<const Generated> gp;
+    DeviceState &ds = prepare(s, &q, gp);
+    const Generated &g = *gp;
+    ConvergeDev &cv = ds.conv;
+    if (!cv.mod) {
+        HIPCHECK(hipModuleLoadData(&cv.mod, code.data()));
+        HIPCHECK(hipModuleGetFunction(&cv.reduce, cv.mod, "pt_converge_reduce"));
+        HIPCHECK(hipModuleGetFunction(&cv.scan, cv.mod, "pt_converge_scan"));
+        HIPCHECK(hipModuleGetFunction(&cv.scatter, cv.mod, "pt_converge_scatter"));
+    }
+    constexpr int kBlock = 256; /* pt_converge.h PTC_BLOCK */
+    const size_t n = (size_t)n0, nwg0 = (n + kBlock - 1) / kBlock;
+    cv.acc.ensure(3 * n), cv.rgb.ensure(3 * n), cv.err.ensure(n), cv.mom.ensure(2 * n);
+    cv.blocks.ensure(n), cv.spp.ensure(n), cv.keep.ensure(n);
+    for (auto &l : cv.list) l.ensure(n);
+    cv.wg.ensure(3 * nwg0), cv.word.ensure(2);
+
+    hipStream_t stream = nullptr;
+    /* timings as render_device keeps them: a call with stats reports itself
+     * alone; one without joins timed renders that wait for their collect */
+    const bool joined = !st && !ds.pending.empty();
+    const bool timed = st || joined;
+    if (st) {
+        for (auto &pr : ds.pending)
+            for (auto e : pr.evs) (void)hipEventDestroy(e);
+        ds.pending.clear();
+    }
+    if (!timed || ds.pending.empty())
+        HIPCHECK(hipMemsetAsync(ds.stats.p, 0, 40 * 8, stream));
+    const int *pix = nullptr, *home = nullptr;
+    if (p->pixels) {
+        HIPCHECK(hipMemcpyAsync(ds.pixels.p, p->pixels, n * 4, hipMemcpyHostToDevice, stream));
+        pix = ds.pixels.p;
+    }
+    PendingRender pr;
+    pr.n_spheres = g.n_spheres, pr.n_planes = g.n_planes;
+    EvGuard eg{pr};
+    const PassLaunch L{s, ds, stream, timed, pr, nullptr, 0};
+    auto launch = [&](hipFunction_t fn, unsigned blocks, PtConvergeHost &a) {
+        void *args[] = {&a};
+        int e0 = (int)pr.evs.size();
+        if (timed)
+            record_event(pr, stream);
+        HIPCHECK(hipModuleLaunchKernel(fn, blocks, 1, 1, kBlock, 1, 1, 0, stream, args, nullptr));
+        if (timed) {
+            record_event(pr, stream);
+            pr.rspans.push_back({e0, e0 + 1});
+        }
+    };
+    PtConvergeHost a;
+    memset(&a, 0, sizeof a);
+    a.cap = p->spp;
+    a.rel_tol = cp->rel_tol, a.abs_tol = cp->abs_tol;
+    a.acc = cv.acc.p, a.mom = cv.mom.p, a.blocks = cv.blocks.p;
+    a.rgb = cv.rgb.p, a.spp = cv.spp.p, a.err = cv.err.p;
+    a.keep = cv.keep.p;
+    a.wg_keep = cv.wg.p, a.wg_capped = cv.wg.p + nwg0, a.wg_off = cv.wg.p + 2 * nwg0;
+    a.word = cv.word.p;
+
+    long long active = n0;
+    int flip = 0;
+    for (int done = 0, next = cp->min_spp; active > 0; done = next, next = (int)std::min<long long>(2ll * done, p->spp)) {
+        /* round: samples [done, next) of the active entries */
+        q.spp = next - done;
+        q.sample_begin = done;
+        const unsigned nwg = (unsigned)((active + kBlock - 1) / kBlock);
+        const long long per_pass = pass_samples(&q, active);
+        a.pix = pix, a.home = home, a.n = active, a.nwg = (int)nwg;
+        for (int s0 = 0; s0 < q.spp; s0 += (int)per_pass) {
+            const int nsamp = (int)std::min<long long>(per_pass, q.spp - s0);
+            a.mode = launch_pass(L, &q, pix, active, s0, nsamp);
+            a.stage = ds.stage.p;
+            a.nsamp = nsamp;
+            a.first = done == 0 && s0 == 0;
+            a.last = s0 + nsamp == q.spp;
+            launch(cv.reduce, nwg, a);
+            pr.samples += (uint64_t)(active * nsamp);
+        }
+        launch(cv.scan, 1, a);
+        uint64_t word[2];
+        HIPCHECK(hipMemcpyAsync(word, cv.word.p, sizeof word, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        cp->rounds++;
+        cp->capped += (int64_t)word[1];
+        const long long left = (long long)word[0];
+        if (left < 0 || left > active)
+            throw Error(PT_ERR_DEVICE, "pt_render_converge: survivor count out of range");
+        if (left > 0) {
+            a.pix_next = cv.list[2 * flip].p, a.home_next = cv.list[2 * flip + 1].p;
+            launch(cv.scatter, nwg, a);
+            pix = a.pix_next, home = a.home_next;
+            flip ^= 1;
+        }
+        active = left;
+    }
+    cp->samples = (int64_t)pr.samples;
+    HIPCHECK(hipMemcpy(rgb_out, cv.rgb.p, 3 * n * 4, hipMemcpyDeviceToHost));
+    if (spp_out)
+        HIPCHECK(hipMemcpy(spp_out, cv.spp.p, n * 4, hipMemcpyDeviceToHost));
+    if (err_out)
+        HIPCHECK(hipMemcpy(err_out, cv.err.p, n * 4, hipMemcpyDeviceToHost));
+    if (!timed)
+        return;
+    eg.kept = true;
+    ds.pending.push_back(std::move(pr));
+    if (st)
         collect_timings(ds, st);
 }
 
@@ -1719,6 +1953,23 @@ int pt_render(pt_scene *s, const pt_render_params *p, float *rgb_out, pt_render_
             g_prof[PT_PROF_KERNEL] = st.kernel_ms * 1e3;
             g_prof[PT_PROF_REDUCE] = st.reduce_ms * 1e3;
         }
+        return PT_OK;
+    });
+}
+
+int pt_render_converge(pt_scene *s, const pt_render_params *p, pt_converge_params *cp, float *rgb_out,
+                       int32_t *spp_out, float *err_out, pt_render_stats *stats)
+{
+    return guard([&] {
+        render_converge(S(s), p, cp, rgb_out, spp_out, err_out, stats);
+        return PT_OK;
+    });
+}
+
+int pt_converge_compile(void)
+{
+    return guard([&] {
+        (void)code_object(converge_generated());
         return PT_OK;
     });
 }

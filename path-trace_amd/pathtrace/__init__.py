@@ -28,7 +28,7 @@ from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject,
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["DeviceScene", "render", "render_device", "prepare",
                                                          "trace_rays", "lcg_state", "trace_pixels_chained",
-                                                         "trace_rays_chained"]
+                                                         "trace_rays_chained", "render_converged"]
 
 ORDERS = {"fast": PT_ORDER_FAST, "reference": PT_ORDER_REFERENCE,
           "strict": PT_ORDER_REFERENCE,
@@ -368,6 +368,35 @@ def render_adaptive(scene, width: int, height: int, spp: int, depth: int, screen
     info.update(traced_pixels=int(ap.traced_pixels), levels=int(ap.levels),
                 lookahead_pixels=int(ap.lookahead_pixels))
     return out, info
+
+
+def render_converged(scene, width: int, height: int, max_spp: int, depth: int, min_spp: int = 64,
+                     rel_tol: float = 0.02, abs_tol: float = 0.0, pixels: Optional[Sequence[int]] = None, screen=None,
+                     seed: int = 0x5EED, device: int = 0, max_buffer_bytes: int = 0):
+    """Every pixel sampled until the standard error of its mean r + g + b is within
+    max(abs_tol, rel_tol * |mean|), or max_spp samples (pt_render_converge): rounds
+    of min_spp, 2 min_spp, 4 min_spp ... samples, each over the pixels that have not
+    stopped.  Returns (image H x W x 3, spp_map H x W int32, err_map H x W float32,
+    info) -- with `pixels`, n x 3, n and n, one per entry.  A pixel that stopped
+    after n samples holds what render(spp=n) gives it, bit for bit; err is its
+    standard error (NaN where its sums are not finite).  info has rounds, samples
+    (traced), capped (stopped only by max_spp) and the render stats."""
+    ds = scene if isinstance(scene, DeviceScene) else DeviceScene(scene)
+    p, keep = make_params(width, height, max_spp, depth, screen, seed, "fast", device, pixels, max_buffer_bytes)
+    cp = _lib.ConvergeParams()
+    cp.min_spp, cp.rel_tol, cp.abs_tol = int(min_spp), float(rel_tol), float(abs_tol)
+    n = len(keep) if keep is not None else width * height
+    out = np.zeros((n, 3), dtype=np.float32)
+    spp = np.zeros(n, dtype=np.int32)
+    err = np.zeros(n, dtype=np.float32)
+    st = RenderStats()
+    _lib.check(_lib.lib().pt_render_converge(ds.handle, ctypes.byref(p), ctypes.byref(cp), out.ctypes.data,
+                                             spp.ctypes.data, err.ctypes.data, ctypes.byref(st)))
+    if keep is None:
+        out, spp, err = out.reshape(height, width, 3), spp.reshape(height, width), err.reshape(height, width)
+    info = st.as_dict()
+    info.update(rounds=int(cp.rounds), samples=int(cp.samples), capped=int(cp.capped))
+    return out, spp, err, info
 
 
 def prepare(scene: DeviceScene, params: RenderParams) -> None:

@@ -36,6 +36,11 @@ class AdaptiveParams(ctypes.Structure):
                 ("lookahead_pixels", ctypes.c_int64)]
 
 
+class ConvergeParams(ctypes.Structure):
+    _fields_ = [("min_spp", ctypes.c_int), ("rel_tol", ctypes.c_float), ("abs_tol", ctypes.c_float),
+                ("rounds", ctypes.c_int), ("samples", ctypes.c_int64), ("capped", ctypes.c_int64)]
+
+
 class TraceParams(ctypes.Structure):
     _fields_ = [("spp", ctypes.c_int), ("depth", ctypes.c_int), ("seed", ctypes.c_uint64), ("order", ctypes.c_int),
                 ("device", ctypes.c_int), ("sample_begin", ctypes.c_int), ("max_buffer_bytes", ctypes.c_int64),
@@ -111,6 +116,9 @@ SIGNATURES = {
     "pt_rank_pixels": (_I, [_I, _I, _I, _I, _I, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "pt_render_adaptive": (_I, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(AdaptiveParams), _P,
                                 ctypes.POINTER(RenderStats)]),
+    "pt_render_converge": (_I, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(ConvergeParams), _P, _P, _P,
+                                ctypes.POINTER(RenderStats)]),
+    "pt_converge_compile": (_I, []),
     "pt_trace_rays": (_I, [_P, ctypes.POINTER(TraceParams), _P, ctypes.c_int64, _P, ctypes.POINTER(RenderStats)]),
     "pt_trace_compile": (_I, [_P, _I]),
     "pt_trace_chains": (_I, [_P, ctypes.POINTER(ChainParams), _P, _P, _P, ctypes.c_int64, _P, _P, _P,
