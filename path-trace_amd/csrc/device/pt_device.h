@@ -626,11 +626,16 @@ struct PrimSpans
     float t0[NP], t1[NP];
     int live[NP];
 };
+/* dead, or strictly separated */
+template <class PS>
+__device__ __forceinline__ int apart(const PS &ps, int x, int y)
+{
+    return (!ps.live[x]) | (!ps.live[y]) | (ps.t1[x] < ps.t0[y]) | (ps.t1[y] < ps.t0[x]);
+}
 template <class PS>
 __device__ __forceinline__ int sep(const PS &ps, int x, int y)
 {
-    return (!ps.live[x]) | (!ps.live[y]) | (ps.t1[x] < ps.t0[y]) | (ps.t1[y] < ps.t0[x]) |
-           ((ps.t1[x] < EPS) & (ps.t1[y] < EPS));
+    return apart(ps, x, y) | ((ps.t1[x] < EPS) & (ps.t1[y] < EPS));
 }
 /* At a Union node (src/union.cpp:84-134) overlapping spans merge into one
  * whose start is the earlier start (the B side's on a tie, :125-132); when
@@ -648,28 +653,56 @@ __device__ __forceinline__ int sep(const PS &ps, int x, int y)
  * quirk's inverted span -- keeps the strict rule.)  Intersection nodes keep
  * the strict rule: separation there means an empty intersection. */
 /* A positive span that ends before EPS (a ray leaving the surface it starts
- * on) is inert: every span the merges above derive from it ends before EPS
- * too -- a Union merge with a span y that reaches EPS ends at y's end with
- * y's ref and starts before EPS like y (src/union.cpp:105-132), a Difference
- * only cuts it (its pieces, and the :124-130 quirk's inverted span, end at or
- * before its end), and the B spans a Difference consumes while passing it end
- * before it, i.e. before any later A span that the checks keep apart from it.
- * The scan (path-trace.h:66-100) skips spans ending before EPS, so the pair
- * checks may ignore it (the first-hit choice never takes it: its t1 < EPS).
- * Only positives: a B-side span that ends before EPS can still trigger the
- * quirk on the A span it overlaps. */
+ * on) is inert.  A Difference only cuts it: its pieces, and the :124-130
+ * quirk's inverted span, end at or before its end, and the B spans a
+ * Difference consumes while passing it end before it, i.e. before any later A
+ * span that the checks keep apart from it.  The scan (path-trace.h:66-100)
+ * skips spans ending before EPS, so a Difference's pair check may ignore an
+ * inert A span (the first-hit choice never takes it: its t1 < EPS).  Only
+ * positives: a B-side span that ends before EPS can still trigger the quirk
+ * on the A span it overlaps.
+ * At a Union an inert span x1 that overlaps a span x2 reaching EPS merges
+ * with it into [x1.t0, x2.t1] (src/union.cpp:105-132): the merge ends at
+ * x2's end with x2's ref, but its START moves back to x1's.  Where only
+ * Unions and transforms lie between the node and the root that changes
+ * nothing: any other span z that meets the part before x2.t0 ends before
+ * x2.t0 <= x1.t1 < EPS (z is kept apart from x2), so the component still
+ * starts before EPS and ends where x2's does, and the scan stops at the same
+ * end.  Below a Difference (D) it does not hold.  On its A side a B span y
+ * wholly behind the origin, separated from x2 and passed against x1 because
+ * both end before EPS, now overlaps the merged span, and with y.t0 <= x1.t0,
+ * y.t1 < x2.t1 the :124-130 quirk sets the merged span's END to y's start --
+ * an inverted span the scan skips, while fast_first_hit reports x2's exit.
+ * (Difference(Union(x1, x2), y) with spans [-2, 0], [-.5, 1.5], [-3, -1]: the
+ * root list is [-2, -3]; on the seam of C3's two left spheres this lost
+ * terms of 8 pixels of the bench frame.)  So below a Difference a Union pair
+ * passes only by separation or by two distinct starts >= EPS (on a B side
+ * the clause would be sound; one flag keeps the rule short).
+ * The same holds for what an Intersection lets through.  Its primitives are
+ * not positive, so no node above checks them, and sep() lets its pairs both
+ * end before EPS: the lens they leave ends before EPS, which a Union chain to
+ * the root absorbs like an inert span.  Below a Difference it does harm: as
+ * the B span of Difference(y, Intersection(x1, x2)) it triggers the quirk on
+ * a y that starts inside it and reaches EPS (spans [-.38, .63] against the
+ * lens [-.73, -.004]: the root list holds the inverted [-.38, -.73], the fast
+ * pass reported y's exit), and merged into an A span it moves that span's
+ * start back as x1 does above.  So below a Difference an Intersection's
+ * pairs must be apart(): it is then empty.
+ * tests/fastcheck.py restates these rules; tools/fastcheck_model.py counts
+ * their disagreements with the merges. */
 enum { NODE_ISECT = 0, NODE_UNION = 1, NODE_DIFF = 2 };
 template <class PS>
 __device__ __forceinline__ int inert(const PS &ps, int x)
 {
     return ps.live[x] & (ps.t1[x] < EPS);
 }
-template <int KIND, class PS>
+/* D: the node lies below some Difference */
+template <int KIND, bool D = false, class PS>
 __device__ __forceinline__ int pair_ok(const PS &ps, int x, int y)
 {
-    int ok = sep(ps, x, y);
+    int ok = (KIND == NODE_ISECT && D) ? apart(ps, x, y) : sep(ps, x, y);
     if (KIND == NODE_UNION)
-        ok |= ((ps.t0[x] >= EPS) & (ps.t0[y] >= EPS) & (ps.t0[x] != ps.t0[y])) | inert(ps, x) | inert(ps, y);
+        ok |= ((ps.t0[x] >= EPS) & (ps.t0[y] >= EPS) & (ps.t0[x] != ps.t0[y])) | (!D & (inert(ps, x) | inert(ps, y)));
     if (KIND == NODE_DIFF)
         ok |= ((ps.t0[x] >= EPS) & (ps.t0[y] > ps.t0[x])) | inert(ps, x);
     return ok;
@@ -811,7 +844,7 @@ struct Sph
     }
     template <class SEL>
     __device__ static constexpr bool clear_ok() { return true; }
-    template <class PS>
+    template <class PS, bool D = false>
     __device__ static __forceinline__ int fast_ok(const PS &) { return 1; }
     __device__ static __forceinline__ V3 normal(int, float t, V3 o, V3 d, const Env &e)
     {
@@ -973,7 +1006,7 @@ struct Pln
     }
     template <class SEL>
     __device__ static constexpr bool clear_ok() { return true; }
-    template <class PS>
+    template <class PS, bool D = false>
     __device__ static __forceinline__ int fast_ok(const PS &) { return 1; }
     __device__ static __forceinline__ V3 normal(int, float, V3, V3, const Env &e)
     {
@@ -1078,11 +1111,12 @@ struct Pln
     {                                                                                               \
         return A::template clear_mask<SEL, NORM>(c.a, q, e) & B::template clear_mask<SEL, NORM>(c.b, q, e); \
     }                                                                                               \
-    template <class PS>                                                                             \
+    /* D: the node lies below some Difference (see inert()) */                                     \
+    template <class PS, bool D = false>                                                             \
     __device__ static __forceinline__ int fast_ok(const PS &ps)                                     \
     {                                                                                               \
-        int ok = A::fast_ok(ps) & B::fast_ok(ps);                                                   \
-        A::each_pos([&](auto x, auto) { B::each_pos([&](auto y, auto) { ok &= pair_ok<KIND>(ps, decltype(x)::value, decltype(y)::value); }); }); \
+        int ok = A::template fast_ok<PS, D || KIND == NODE_DIFF>(ps) & B::template fast_ok<PS, D || KIND == NODE_DIFF>(ps); \
+        A::each_pos([&](auto x, auto) { B::each_pos([&](auto y, auto) { ok &= pair_ok<KIND, D>(ps, decltype(x)::value, decltype(y)::value); }); }); \
         return ok;                                                                                  \
     }                                                                                               \
     __device__ static __forceinline__ V3 normal(int prim, float t, V3 o, V3 d, const Env &e)       \
@@ -1891,8 +1925,8 @@ struct Xf
     }
     template <class SEL>
     __device__ static constexpr bool clear_ok() { return C::template clear_ok<SEL>(); }
-    template <class PS>
-    __device__ static __forceinline__ int fast_ok(const PS &ps) { return C::fast_ok(ps); }
+    template <class PS, bool D = false>
+    __device__ static __forceinline__ int fast_ok(const PS &ps) { return C::template fast_ok<PS, D>(ps); }
     __device__ static __forceinline__ V3 normal(int prim, float t, V3 o, V3 d, const Env &e)
     {
         V3 n = C::normal(prim, t, m_apply(e.P + MOFF, o), m_lin(e.P + MOFF, d), e);

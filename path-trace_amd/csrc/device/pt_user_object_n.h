@@ -146,7 +146,7 @@ struct UObjN
     }
     template <class SEL>
     __device__ static constexpr bool clear_ok() { return true; }
-    template <class PS>
+    template <class PS, bool D = false>
     __device__ static __forceinline__ int fast_ok(const PS &) { return 1; }
     __device__ static __forceinline__ V3 normal(int prim, float t, V3 o, V3 d, const Env &e)
     {

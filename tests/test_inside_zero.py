@@ -22,7 +22,8 @@ Difference-bearing scenes the suite already freezes, not as evidence for the rul
 never fires in them (mid 2 550 966 / 2 550 966 for s = 1, 0 / 0 for s = 2, 4, 5), and of the lattice scenes
 lat1 moves by only 283 of 932 462 mid children.  At 1920 x 1080 x 1024 spp 8 pixels of C3's frame differ
 between the arms, through the mid pass's fast check and not through the rule
-(profiles/round10/frame_diff_passes.txt); no render here is large enough to reach such a child.
+(profiles/round10/frame_diff_passes.txt); no render here is large enough to reach such a child
+(tests/test_fastcheck.py renders those pixels, since the fix of that check).
 
 The modules are listed in tests/precompile_inside_zero.py."""
 import os
