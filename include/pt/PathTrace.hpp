@@ -1491,6 +1491,37 @@ public:
         return out;
     }
 
+    /* Guide buffers beside the beauty image (pt_render_guides): per pixel -- or
+     * entry of pixels -- the means over its st.sampleCount camera samples of
+     * what the first hit shows, each summed in float from +0 in sample order and
+     * divided by the sample count; a sample that misses adds 0.  emission is
+     * render()'s frame at rayDepth 0 in PT_ORDER_REFERENCE, bit for bit.
+     * st.rayDepth, st.order and st.maxBufferBytes are ignored. */
+    struct Guides
+    {
+        std::vector<Color> emission, albedo; /* the emissive and the reflect colour at the hit */
+        std::vector<Vector3D> normal;        /* the shading normal, not normalised again        */
+        std::vector<float> t, coverage;      /* the hit parameter (misses as 0); hits / samples */
+        std::vector<int32_t> material;       /* pt_id at the first sample's hit, or -1          */
+    };
+    Guides renderGuides(const Settings &st, const int32_t *pixels = nullptr, int64_t npixels = 0) const
+    {
+        pt_render_params p = params(st, pixels, npixels);
+        const size_t n = (size_t)(pixels ? npixels : (int64_t)st.width * st.height);
+        Guides g;
+        g.emission.resize(n), g.albedo.resize(n), g.normal.resize(n);
+        g.t.resize(n), g.coverage.resize(n), g.material.resize(n);
+        static_assert(sizeof(Vector3D) == 3 * sizeof(float), "Vector3D must be 3 packed floats");
+        pt_guide_buffers b = {};
+        b.emission = reinterpret_cast<float *>(g.emission.data());
+        b.albedo = reinterpret_cast<float *>(g.albedo.data());
+        b.normal = reinterpret_cast<float *>(g.normal.data());
+        b.t = g.t.data(), b.coverage = g.coverage.data(), b.material = g.material.data();
+        if (n) /* an empty list: nothing to point at, nothing to do */
+            ptCheck(pt_render_guides(s_, &p, &b));
+        return g;
+    }
+
     /* Compile / upload everything a render with these settings needs. */
     void prepare(const Settings &st) const
     {
@@ -1514,6 +1545,45 @@ public:
 private:
     pt_scene *s_;
 };
+
+/* What traceRay sees at the first surface (include/path-trace.h:66-129) along
+ * each ray, on the device (pt_query_hits): hit or miss, entry or exit of a span,
+ * the ray parameter, the shading normal (negated on an exit, not normalised
+ * again), the point origin + t * dir, the Material and its ior.  On a miss
+ * material is null and every number 0.  path: PT_HIT_FAST (the fast checks, the
+ * lazy merge where they cannot decide) or PT_HIT_MERGE (the lazy merge alone);
+ * both give the same bits. */
+struct FirstHit
+{
+    bool hit, exit;
+    float t;
+    Vector3D normal, pos;
+    const Material *material;
+    float ior;
+};
+inline std::vector<FirstHit> firstHits(const Object &world, const std::vector<Ray> &rays, int path = PT_HIT_FAST,
+                                       int device = 0)
+{
+    DeviceQueryScene q;
+    ptCheck(pt_set_root(q.s, world.flatten(q.f)));
+    std::vector<float> r(6 * rays.size());
+    for (size_t k = 0; k < rays.size(); k++) {
+        const Ray &y = rays[k];
+        float *f = &r[6 * k];
+        f[0] = y.origin.x, f[1] = y.origin.y, f[2] = y.origin.z, f[3] = y.dir.x, f[4] = y.dir.y, f[5] = y.dir.z;
+    }
+    std::vector<pt_hit> h(rays.size());
+    if (!rays.empty())
+        ptCheck(pt_query_hits(q.s, r.data(), (int64_t)rays.size(), path, h.data(), nullptr, nullptr, device));
+    std::vector<FirstHit> out;
+    out.reserve(h.size());
+    for (const pt_hit &x : h) {
+        FirstHit o = {x.hit != 0, x.exit != 0, x.t, Vector3D(x.normal[0], x.normal[1], x.normal[2]),
+                      Vector3D(x.pos[0], x.pos[1], x.pos[2]), x.hit ? q.f.material_of(x.material) : nullptr, x.ior};
+        out.push_back(o);
+    }
+    return out;
+}
 
 /* SDL_SaveBMP of the demo's tone map (src/test.cpp:1037-1059). */
 inline void writeBMP(const std::string &path, const std::vector<Color> &rgb, int w, int h, int count = 1)

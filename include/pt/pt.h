@@ -252,6 +252,8 @@ int pt_rank_pixels(int width, int height, int rank, int world, int tile, int32_t
                              or PT_CALL_KERNEL_TIME is set)                                   */
 #define PT_PROF_REDUCE 6  /* pt_reduce by HIP events (the same condition)                     */
 #define PT_PROF_N 7
+/* pt_query_hits and pt_render_guides record PT_PROF_TOTAL and PT_PROF_KERNEL
+ * (their one launch, by HIP events) the same way; the other phases read 0. */
 int pt_call_profile(double *out, int n);
 
 /* Device variant: writes W*H*3 floats into device memory fb (full frame,
@@ -501,6 +503,64 @@ int pt_tex_eval(pt_scene *s, pt_id tex, const float *points, int64_t n, float *r
  * (-1: the root, when tex < 0; -2: none) and/or tex (-1: none), without a
  * device. */
 int pt_query_compile(pt_scene *s, pt_id obj, pt_id tex);
+
+/* What traceRay sees at the first surface (include/path-trace.h:66-129), for n
+ * caller rays (6 floats each: origin xyz, direction xyz, not normalised) against
+ * the scene root, one ray per lane of the scene's guides module
+ * (path-trace_amd/csrc/device/pt_guides.h).  path chooses the query:
+ * PT_HIT_MERGE the lazy merge of the CSG tree, traceRay's scan itself;
+ * PT_HIT_FAST every primitive's span and the fast checks first and the lazy
+ * merge only on the rays the checks cannot decide, as the render kernel's spine
+ * and lane queries run.  Both give the same bits in every field.
+ * out[i]: hit = 0 / 1 (a span list that runs out and a span at or beyond 1e20
+ * are both 0); exit = 1 when the hit is a span's end; t the ray parameter;
+ * normal the shading normal (the span's, negated on an exit; not normalised
+ * again); pos = origin + t * direction; material its pt_id; ior the material's
+ * own.  On a miss hit = exit = 0, material = -1 and every float is +0.
+ * shade_out (NULL, or 11 floats per ray) receives the material's five texture
+ * lookups at pos, unclamped: emissive rgb, reflect rgb, transmit rgb, scatter
+ * coefficient, transmit-reflect coefficient (:101-129); +0 on a miss.
+ * decided (NULL, or one int per ray) receives the fast check's verdict for the
+ * ray, hit or miss: 1 where span_first_hit's answer stood, 0 where the ray took
+ * the lazy merge; always 0 on PT_HIT_MERGE.
+ * Rays must have finite components and a non-zero direction, as for
+ * pt_trace_rays.  Every argument is checked before a device is touched:
+ * PT_ERR_ARG names the argument in pt_last_error(). */
+#define PT_HIT_FAST 0
+#define PT_HIT_MERGE 1
+typedef struct pt_hit {
+    int32_t hit, exit, material;
+    float t, normal[3], pos[3], ior;
+} pt_hit;
+int pt_query_hits(pt_scene *s, const float *rays, int64_t n, int path, pt_hit *out, float *shade_out,
+                  int32_t *decided, int device);
+
+/* Guide buffers beside the beauty image: per pixel entry, means over the
+ * camera samples of what the first hit shows.  Sample s = p->sample_begin ..
+ * p->sample_begin + p->spp - 1 of pixel index y * grid_width + x draws its camera
+ * ray from the engine keyed (p->seed, index, s) exactly as pt_render does, and is
+ * queried with PT_HIT_FAST.  Summation rule: each quantity is accumulated in
+ * f32 from +0 in sample order, acc = acc + x_s, a miss adding +0, and divided by
+ * (float)spp at the end.  So `emission` is pt_render's frame at depth 0 in
+ * PT_ORDER_REFERENCE, bit for bit.  Planes (host memory; NULL = skip):
+ * emission, albedo (the reflect colour) and normal (the shading normal, not
+ * normalised again) 3 floats per entry; t (misses as 0) and coverage (hits /
+ * spp) 1 float; material 1 int, the pt_id at the first sample's hit or -1.
+ * Entries are p->pixels (compact: entry k at k) or the whole frame, row-major.
+ * Honoured: width, height, spp, screen_w / _h / _dist, seed, device, pixels,
+ * npixels, grid_width, sample_begin; depth, order, sum_only and max_buffer_bytes
+ * are ignored.  Every argument is checked before a device is touched:
+ * PT_ERR_ARG names the argument in pt_last_error(). */
+typedef struct pt_guide_buffers {
+    float *emission, *albedo, *normal, *t, *coverage;
+    int32_t *material;
+} pt_guide_buffers;
+int pt_render_guides(pt_scene *s, const pt_render_params *p, const pt_guide_buffers *out);
+/* JIT-compile (or fetch from the code-object cache) the scene's guides module
+ * -- pt_query_hits' and pt_render_guides' kernels -- without touching a GPU. */
+int pt_guides_compile(pt_scene *s);
+/* Its code-object key (as pt_scene_module_key: hex string, thread-local). */
+const char *pt_scene_guides_key(pt_scene *s);
 
 /* Device self-test: the megakernel's exact fast paths for f32 sqrt / '/' /
  * normalize against the compiler's correctly rounded ones on n hashed inputs.

@@ -402,9 +402,9 @@ uint64_t fnv1a(const std::string &s, uint64_t h = 1469598103934665603ull)
     return h;
 }
 
-} // namespace
-
-Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
+/* The module of one (scene, depth, kind).  guides: the guides kind
+ * (generate_guides) -- the same Scene text, none of the render kernels' knobs. */
+Generated generate_kind(const SceneImpl &s, int depth, bool rays, bool chain, bool guides)
 {
     if (s.root < 0)
         throw Error(PT_ERR_ARG, "scene has no root object (pt_set_root)");
@@ -471,20 +471,22 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
         }
     }
     /* the ray-list module of pt_trace_rays: items are caller rays, not camera samples */
-    if (rays)
+    if (guides)
+        ; /* no render kernel: none of its knobs (the Scene below reads PT_AXIS_SHARE alone) */
+    else if (rays)
         src << "#define PT_RAYS 1\n";
     /* the chained module of pt_trace_chains: one launch traces one sample of each chain on the
      * chain's own engine state (pt_device.h PT_CHAIN).  Built as the scene's default render module
      * is -- lane_sample plus lane resume or the wave walk -- whatever lane walk the scene asks for */
-    if (chain)
+    if (chain && !guides)
         src << "#define PT_CHAIN 1\n";
-    const int lane_walk = chain ? 0 : s.lane_walk;
-    const bool lane_scatter = !chain && s.lane_scatter;
+    const int lane_walk = chain || guides ? 0 : s.lane_walk;
+    const bool lane_scatter = !chain && !guides && s.lane_scatter;
     /* per-scene occupancy (pt_scene_set_occupancy): the launch bounds' workgroups per CU */
-    if (s.wg_per_cu > 0)
+    if (s.wg_per_cu > 0 && !guides)
         src << "#define PT_MIN_WAVES " << s.wg_per_cu << "\n";
     /* per-scene spine query form (pt_scene_set_fast_spine) */
-    if (s.fast_spine)
+    if (s.fast_spine && !guides)
         src << "#define PT_FAST_SPINE 1\n";
     /* per-scene lane walk of scatter-free trees (pt_scene_set_lane_walk) */
     if (lane_walk > 0)
@@ -498,7 +500,7 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
      * for elsewhere, the module is built without it.  Auto (-1) follows
      * LANE_RESUME_AUTO, decided by the C3 measurement */
     constexpr bool LANE_RESUME_AUTO = true;
-    if ((s.lane_resume < 0 ? LANE_RESUME_AUTO : s.lane_resume > 0) && bursts_all_leaf && lane_walk == 0 &&
+    if (!guides && (s.lane_resume < 0 ? LANE_RESUME_AUTO : s.lane_resume > 0) && bursts_all_leaf && lane_walk == 0 &&
         !lane_scatter)
         src << "#define PT_LANE_RESUME 1\n";
     /* Difference-free trees skip a sphere's root and divisions when no lane of
@@ -510,7 +512,9 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
     /* axes whose unit-normal planes share the ray's reciprocal (Pln UNIT) */
     if (axis_share)
         src << "#define PT_AXIS_SHARE " << axis_share << "\n";
-    if (root.find("Diff<") == std::string::npos)
+    if (guides)
+        ;
+    else if (root.find("Diff<") == std::string::npos)
         src << "#ifndef PT_SPHERE_SKIP\n#define PT_SPHERE_SKIP 1\n#endif\n"
             << "#ifndef PT_KATT\n#define PT_KATT 6\n#endif\n";
     /* trees with a Difference and no lane walks (C3): 10 attempts per lane
@@ -526,7 +530,7 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
      * profiles/round5/ab_sched_maxocc.txt); not when the PT_JIT_OPTIONS hook
      * names a strategy of its own (an LLVM option may occur once) */
     const char *jit_opts = getenv("PT_JIT_OPTIONS");
-    const bool maxocc = root.find("Diff<") != std::string::npos && lane_walk == 0 && !lane_scatter &&
+    const bool maxocc = !guides && root.find("Diff<") != std::string::npos && lane_walk == 0 && !lane_scatter &&
                         !(jit_opts && strstr(jit_opts, "sched-strategy"));
     src << device_library_source(chain) << "\n";
     if (!g.user_obj.empty())
@@ -592,7 +596,10 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
     src << "  __device__ static __forceinline__ float ior(int m, const Env &e) { return e.P[" << ior_off
         << " + m]; }\n";
     src << "};\n} // namespace ptgen\n";
-    src << (chain ? "PT_DEFINE_CHAIN_KERNEL" : "PT_DEFINE_KERNELS") << "(ptgen::Scene, " << maxd << ")\n";
+    if (guides)
+        src << device_guides_source() << "\nPT_DEFINE_GUIDES(ptgen::Scene)\n";
+    else
+        src << (chain ? "PT_DEFINE_CHAIN_KERNEL" : "PT_DEFINE_KERNELS") << "(ptgen::Scene, " << maxd << ")\n";
 
     Generated out;
     out.source = src.str();
@@ -615,6 +622,15 @@ Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
     out.key = key;
     return out;
 }
+
+} // namespace
+
+Generated generate(const SceneImpl &s, int depth, bool rays, bool chain)
+{
+    return generate_kind(s, depth, rays, chain, false);
+}
+
+Generated generate_guides(const SceneImpl &s) { return generate_kind(s, 0, false, false, true); }
 
 Generated generate_query(const SceneImpl &s, int obj, int tex)
 {

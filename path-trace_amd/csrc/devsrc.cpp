@@ -78,4 +78,11 @@ std::string device_converge_source()
         ;
     return src;
 }
+std::string device_guides_source()
+{
+    static const char src[] =
+#include "pt_guides_src.inc"
+        ;
+    return src;
+}
 } // namespace pt

@@ -118,6 +118,11 @@ struct Generated
  * chain: the module of pt_trace_chains (PT_CHAIN), whose items draw from a
  * chain's own engine state, one sample of each chain per launch */
 Generated generate(const SceneImpl &s, int depth, bool rays = false, bool chain = false);
+/* The guides module of pt_query_hits / pt_render_guides: the scene's full
+ * `ptgen::Scene` as generate() writes it -- root type and material dispatchers
+ * -- under none of the render kernels' per-scene knobs, followed by
+ * device/pt_guides.h and its two kernels instead of the render kernels. */
+Generated generate_guides(const SceneImpl &s);
 
 /* pt_trace_chains' step sequence.  Chain c has len[c] * spp steps; step t runs
  * the chains with more than t steps.  order = the chain ids by descending
@@ -157,6 +162,7 @@ std::string device_library_source(bool chain = false);
 std::string device_user_object_source(); /* embedded pt_user_object.h (scenes with user objects) */
 std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scenes with multi-span user objects) */
 std::string device_converge_source(); /* embedded pt_converge.h (pt_render_converge's scene-independent module) */
+std::string device_guides_source(); /* embedded pt_guides.h (the guides module: pt_query_hits, pt_render_guides) */
 
 } // namespace pt
 

@@ -759,11 +759,13 @@ struct Fnv
             bytes(v, n);
     }
 };
-std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays, bool chain = false)
+std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays, bool chain = false,
+                                           bool guides = false)
 {
+    auto make = [&] { return guides ? generate_guides(s) : generate(s, depth, rays, chain); };
     if (const char *hdr = getenv("PT_DEVICE_HEADER")) /* experiment hook: the file may change under us */
         if (*hdr)
-            return std::make_shared<const Generated>(generate(s, depth, rays, chain));
+            return std::make_shared<const Generated>(make());
     Fnv f;
     for (const ObjRec &o : s.objects) {
         f.add(o.kind), f.add(o.mat), f.add(o.a), f.add(o.b);
@@ -794,14 +796,14 @@ std::shared_ptr<const Generated> generated(SceneImpl &s, int depth, bool rays, b
     f.add(s.root), f.add(s.default_tex[0]), f.add(s.default_tex[1]);
     f.add(s.wg_per_cu), f.add(s.fast_spine), f.add(s.lane_walk), f.add(s.lane_scatter);
     f.add(s.lane_resume);
-    f.add(depth), f.add(rays), f.add(chain);
+    f.add(depth), f.add(rays), f.add(chain), f.add(guides);
     f.str(getenv("PT_DEVICE_DEFINES")), f.str(getenv("PT_JIT_OPTIONS"));
     auto it = s.gen_cache.find(f.h);
     if (it != s.gen_cache.end())
         return it->second;
     if (s.gen_cache.size() >= 16)
         s.gen_cache.clear();
-    auto g = std::make_shared<const Generated>(generate(s, depth, rays, chain));
+    auto g = std::make_shared<const Generated>(make());
     s.gen_cache[f.h] = g;
     return g;
 }
@@ -2557,6 +2559,228 @@ int pt_query_compile(pt_scene *s, pt_id obj, pt_id tex)
         (void)code_object(generate_query(sc, obj < 0 ? -1 : obj, tex));
         return PT_OK;
     });
+}
+
+namespace
+{
+/* One launch of a guides-module kernel between two HIP events, waited for: the
+ * kernel's device time goes to pt_call_profile's PT_PROF_KERNEL (microseconds) */
+void guides_launch(hipFunction_t fn, long long n, void **args)
+{
+    hipEvent_t a = nullptr, b = nullptr;
+    struct Ev
+    {
+        hipEvent_t &a, &b;
+        ~Ev()
+        {
+            if (a)
+                (void)hipEventDestroy(a);
+            if (b)
+                (void)hipEventDestroy(b);
+        }
+    } ev{a, b};
+    HIPCHECK(hipEventCreate(&a));
+    HIPCHECK(hipEventCreate(&b));
+    HIPCHECK(hipEventRecord(a, nullptr));
+    HIPCHECK(hipModuleLaunchKernel(fn, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, nullptr, args, nullptr));
+    HIPCHECK(hipEventRecord(b, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, a, b));
+    g_prof[PT_PROF_KERNEL] = (double)ms * 1e3;
+}
+} // namespace
+
+/* pt_query_hits: the guides module's pt_hits kernel (device/pt_guides.h), one
+ * ray per lane into planar device arrays, assembled into pt_hit records here */
+int pt_query_hits(pt_scene *s, const float *rays, int64_t n, int path, pt_hit *out, float *shade_out,
+                  int32_t *decided, int device)
+{
+    const double t0 = now_us();
+    for (double &v : g_prof) v = 0.0;
+    return guard([&] {
+        SceneImpl &sc = S(s);
+        if (n < 0 || n >= (1ll << 31))
+            throw Error(PT_ERR_ARG, "pt_query_hits: n must be in [0, 2^31)");
+        if (path != PT_HIT_FAST && path != PT_HIT_MERGE)
+            throw Error(PT_ERR_ARG, "pt_query_hits: path must be PT_HIT_FAST or PT_HIT_MERGE");
+        if (device < 0)
+            throw Error(PT_ERR_ARG, "pt_query_hits: device is negative");
+        if (n > 0 && !rays)
+            throw Error(PT_ERR_ARG, "pt_query_hits: rays is null");
+        if (n > 0 && !out)
+            throw Error(PT_ERR_ARG, "pt_query_hits: out is null");
+        for (int64_t k = 0; k < n; k++) {
+            /* as pt_trace_rays: Ray(o, d) asserts d != 0, and the axis-aligned plane forms need finite operands */
+            for (int c = 0; c < 6; c++)
+                if (!std::isfinite(rays[6 * k + c]))
+                    throw Error(PT_ERR_ARG,
+                                "pt_query_hits: rays[" + std::to_string(k) + "] has a non-finite origin or direction");
+            if (rays[6 * k + 3] == 0.0f && rays[6 * k + 4] == 0.0f && rays[6 * k + 5] == 0.0f)
+                throw Error(PT_ERR_ARG, "pt_query_hits: rays[" + std::to_string(k) + "] has a zero direction");
+        }
+        static_assert(sizeof(pt_hit) == 44, "pt_hit is eleven 4-byte words");
+        std::shared_ptr<const Generated> gp = generated(sc, 0, false, false, true);
+        const Generated &g = *gp;
+        if (n == 0)
+            return PT_OK;
+        DeviceGuard dg;
+        QueryModule &q = query_module(sc, g, device);
+        Scratch sm;
+        const size_t N = (size_t)n;
+        float *dr = (float *)sm.alloc(N * 24);
+        int *dhit = (int *)sm.alloc(N * 4), *dex = (int *)sm.alloc(N * 4), *ddec = (int *)sm.alloc(N * 4);
+        int *dmat = (int *)sm.alloc(N * 4);
+        float *dt = (float *)sm.alloc(N * 4), *dn = (float *)sm.alloc(N * 12), *dp = (float *)sm.alloc(N * 12);
+        float *dior = (float *)sm.alloc(N * 4);
+        float *dsh = shade_out ? (float *)sm.alloc(N * 44) : nullptr;
+        HIPCHECK(hipMemcpy(dr, rays, N * 24, hipMemcpyHostToDevice));
+        const float *Pp = q.P.p;
+        const PtImageDev *ip = q.imgs.p;
+        long long nn = n;
+        void *args[] = {&Pp, &ip, &dr, &nn, &path, &dhit, &dex, &ddec, &dmat, &dt, &dn, &dp, &dior, &dsh};
+        guides_launch(q.fn("pt_hits"), n, args);
+        std::vector<int32_t> hhit(N), hex(N), hmat(N);
+        std::vector<float> ht(N), hn(3 * N), hp(3 * N), hior(N);
+        HIPCHECK(hipMemcpy(hhit.data(), dhit, N * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hex.data(), dex, N * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hmat.data(), dmat, N * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(ht.data(), dt, N * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hn.data(), dn, N * 12, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hp.data(), dp, N * 12, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hior.data(), dior, N * 4, hipMemcpyDeviceToHost));
+        if (decided)
+            HIPCHECK(hipMemcpy(decided, ddec, N * 4, hipMemcpyDeviceToHost));
+        if (shade_out)
+            HIPCHECK(hipMemcpy(shade_out, dsh, N * 44, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < N; i++) {
+            pt_hit &h = out[i];
+            h.hit = hhit[i], h.exit = hex[i];
+            /* compact material index -> the scene's material id */
+            h.material = hmat[i] < 0 ? -1 : g.mat_ids.at((size_t)hmat[i]);
+            h.t = ht[i], h.ior = hior[i];
+            for (int c = 0; c < 3; c++) h.normal[c] = hn[3 * i + c], h.pos[c] = hp[3 * i + c];
+        }
+        g_prof[PT_PROF_TOTAL] = now_us() - t0;
+        return PT_OK;
+    });
+}
+
+namespace
+{
+struct PtGuideLaunchHost /* must match pt_guides.h PtGuideLaunch */
+{
+    uint64_t seed;
+    int W, H;
+    float sw, sh, dist;
+    int gw, s0, spp;
+    float *emission, *albedo, *normal, *t, *coverage;
+    int *material;
+};
+} // namespace
+
+/* pt_render_guides: the guides module's pt_guides kernel, one pixel entry per
+ * lane with its sample loop inside the lane */
+int pt_render_guides(pt_scene *s, const pt_render_params *p, const pt_guide_buffers *out)
+{
+    const double t0 = now_us();
+    for (double &v : g_prof) v = 0.0;
+    return guard([&] {
+        SceneImpl &sc = S(s);
+        if (!p)
+            throw Error(PT_ERR_ARG, "pt_render_guides: p is null");
+        if (!out)
+            throw Error(PT_ERR_ARG, "pt_render_guides: out is null");
+        if (!out->emission && !out->albedo && !out->normal && !out->t && !out->coverage && !out->material)
+            throw Error(PT_ERR_ARG, "pt_render_guides: out has every plane null");
+        if (p->device < 0)
+            throw Error(PT_ERR_ARG, "pt_render_guides: p->device is negative");
+        if (p->pixels && p->npixels < 0)
+            throw Error(PT_ERR_ARG, "pt_render_guides: p->npixels is negative");
+        if (p->pixels && p->width > 0 && p->height > 0) {
+            const int64_t limit = p->grid_width ? (int64_t)INT32_MAX : (int64_t)p->width * p->height;
+            for (int64_t k = 0; k < p->npixels; k++)
+                if (p->pixels[k] < 0 || p->pixels[k] >= limit)
+                    throw Error(PT_ERR_ARG, "pt_render_guides: p->pixels[" + std::to_string(k) + "] is out of range");
+        }
+        pt_render_params v = *p; /* depth, order, sum_only and max_buffer_bytes are ignored */
+        v.depth = 0, v.order = PT_ORDER_REFERENCE, v.sum_only = 0, v.max_buffer_bytes = 0;
+        try {
+            validate(&v);
+        } catch (const Error &e) {
+            throw Error(e.code, std::string("pt_render_guides: p: ") + e.what());
+        }
+        std::shared_ptr<const Generated> gp = generated(sc, 0, false, false, true);
+        const Generated &g = *gp;
+        const long long n = p->pixels ? (long long)p->npixels : (long long)p->width * p->height;
+        if (n == 0)
+            return PT_OK;
+        DeviceGuard dg;
+        QueryModule &q = query_module(sc, g, p->device);
+        Scratch sm;
+        const size_t N = (size_t)n;
+        PtGuideLaunchHost gl;
+        memset(&gl, 0, sizeof gl);
+        gl.seed = p->seed;
+        gl.W = p->width, gl.H = p->height;
+        gl.sw = p->screen_w, gl.sh = p->screen_h, gl.dist = p->screen_dist;
+        gl.gw = p->grid_width > 0 ? p->grid_width : p->width;
+        gl.s0 = p->sample_begin, gl.spp = p->spp;
+        gl.emission = out->emission ? (float *)sm.alloc(N * 12) : nullptr;
+        gl.albedo = out->albedo ? (float *)sm.alloc(N * 12) : nullptr;
+        gl.normal = out->normal ? (float *)sm.alloc(N * 12) : nullptr;
+        gl.t = out->t ? (float *)sm.alloc(N * 4) : nullptr;
+        gl.coverage = out->coverage ? (float *)sm.alloc(N * 4) : nullptr;
+        gl.material = out->material ? (int *)sm.alloc(N * 4) : nullptr;
+        int *dpix = nullptr;
+        if (p->pixels) {
+            dpix = (int *)sm.alloc(N * 4);
+            HIPCHECK(hipMemcpy(dpix, p->pixels, N * 4, hipMemcpyHostToDevice));
+        }
+        const float *Pp = q.P.p;
+        const PtImageDev *ip = q.imgs.p;
+        long long nn = n;
+        void *args[] = {&Pp, &ip, &dpix, &nn, &gl};
+        guides_launch(q.fn("pt_guides"), n, args);
+        if (out->emission)
+            HIPCHECK(hipMemcpy(out->emission, gl.emission, N * 12, hipMemcpyDeviceToHost));
+        if (out->albedo)
+            HIPCHECK(hipMemcpy(out->albedo, gl.albedo, N * 12, hipMemcpyDeviceToHost));
+        if (out->normal)
+            HIPCHECK(hipMemcpy(out->normal, gl.normal, N * 12, hipMemcpyDeviceToHost));
+        if (out->t)
+            HIPCHECK(hipMemcpy(out->t, gl.t, N * 4, hipMemcpyDeviceToHost));
+        if (out->coverage)
+            HIPCHECK(hipMemcpy(out->coverage, gl.coverage, N * 4, hipMemcpyDeviceToHost));
+        if (out->material) {
+            HIPCHECK(hipMemcpy(out->material, gl.material, N * 4, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < N; k++)
+                if (out->material[k] >= 0)
+                    out->material[k] = g.mat_ids.at((size_t)out->material[k]);
+        }
+        g_prof[PT_PROF_TOTAL] = now_us() - t0;
+        return PT_OK;
+    });
+}
+
+int pt_guides_compile(pt_scene *s)
+{
+    return guard([&] {
+        (void)code_object(generate_guides(S(s)));
+        return PT_OK;
+    });
+}
+
+const char *pt_scene_guides_key(pt_scene *s)
+{
+    thread_local std::string k;
+    try {
+        k = code_object_key(generate_guides(S(s)));
+    } catch (std::exception &e) {
+        set_error(e.what());
+        k.clear();
+    }
+    return k.c_str();
 }
 
 /* Runs the device self-test of the exact sqrt/div fast paths on n inputs;

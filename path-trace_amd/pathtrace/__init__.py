@@ -28,11 +28,16 @@ from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject,
 
 __all__ = [n for n in dir() if not n.startswith("_")] + ["DeviceScene", "render", "render_device", "prepare",
                                                          "trace_rays", "lcg_state", "trace_pixels_chained",
-                                                         "trace_rays_chained", "render_converged"]
+                                                         "trace_rays_chained", "render_converged",
+                                                         "render_guides"]
 
 ORDERS = {"fast": PT_ORDER_FAST, "reference": PT_ORDER_REFERENCE,
           "strict": PT_ORDER_REFERENCE,
           "group64": PT_ORDER_FAST}  # deprecated name of "fast" (rounds 1-2)
+
+
+HIT_PATHS = {"fast": _lib.PT_HIT_FAST, "merge": _lib.PT_HIT_MERGE}
+GUIDE_PLANES = {"emission": 3, "albedo": 3, "normal": 3, "t": 1, "coverage": 1, "material": 1}
 
 
 class DeviceScene:
@@ -189,6 +194,40 @@ class DeviceScene:
         for t in textures:
             tid = int(t) if isinstance(t, (int, np.integer)) else self._tex(t)
             _lib.check(_lib.lib().pt_query_compile(self._h, -2, tid))
+
+    def query_hits(self, rays, path: str = "fast", shade: bool = False, device: int = 0) -> dict:
+        """What traceRay sees at the first surface for each ray (n x 6: origin,
+        direction), on the device (pt_query_hits).  path "merge" runs the lazy
+        merge, "fast" the fast checks with the merge as their fallback; both give
+        the same bits.  Returns a dict of arrays: hit, exit, material (pt_id, -1
+        on a miss) int32[n]; t, ior float32[n]; normal, pos float32[n, 3];
+        decided int32[n], the fast check's verdict (0 on "merge"); with shade,
+        shade float32[n, 11]: emissive, reflect and transmit rgb, scatter and
+        transmit-reflect coefficients at pos."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = len(rays)
+        out = np.zeros(n, dtype=_lib.HIT_DTYPE)
+        dec = np.zeros(n, dtype=np.int32)
+        sh = np.zeros((n, 11), dtype=np.float32) if shade else None
+        _lib.check(_lib.lib().pt_query_hits(self._h, rays.ctypes.data, n, HIT_PATHS[path], out.ctypes.data,
+                                            sh.ctypes.data if shade else None, dec.ctypes.data, int(device)))
+        res = {k: np.ascontiguousarray(out[k]) for k in _lib.HIT_DTYPE.names}
+        res["decided"] = dec
+        if shade:
+            res["shade"] = sh
+        return res
+
+    def compile_guides(self) -> str:
+        """Compile the guides module -- query_hits' and render_guides' kernels --
+        without a device; returns its code-object key (pt_scene_guides_key)."""
+        _lib.check(_lib.lib().pt_guides_compile(self._h))
+        return self.guides_key()
+
+    def guides_key(self) -> str:
+        k = _lib.lib().pt_scene_guides_key(self._h).decode()
+        if not k:
+            raise PtError(_lib.lib().pt_last_error().decode())
+        return k
 
     def kernel_key(self, depth: int) -> str:
         """The code-object key of this scene's render kernel at `depth`
@@ -397,6 +436,33 @@ def render_converged(scene, width: int, height: int, max_spp: int, depth: int, m
     info = st.as_dict()
     info.update(rounds=int(cp.rounds), samples=int(cp.samples), capped=int(cp.capped))
     return out, spp, err, info
+
+
+def render_guides(scene, width: int, height: int, spp: int, pixels: Optional[Sequence[int]] = None, screen=None,
+                  seed: int = 0x5EED, device: int = 0, grid_width: int = 0, sample_begin: int = 0,
+                  planes: Optional[Sequence[str]] = None) -> dict:
+    """Guide buffers beside the beauty image (pt_render_guides): per pixel, the
+    means over its spp camera samples of what the first hit shows -- emission,
+    albedo, normal (H x W x 3), t and coverage (H x W, float32) and material
+    (H x W int32: the pt_id at the first sample's hit, or -1); with `pixels`, one
+    row per entry.  Each is summed in float32 from +0 in sample order and divided
+    by spp, so emission is render(depth=0, order="reference") bit for bit.
+    planes: the names to compute (default: all six)."""
+    ds = scene if isinstance(scene, DeviceScene) else DeviceScene(scene)
+    p, keep = make_params(width, height, spp, 0, screen, seed, "reference", device, pixels, 0, grid_width,
+                          sample_begin)
+    n = len(keep) if keep is not None else width * height
+    names = list(GUIDE_PLANES) if planes is None else list(planes)
+    res, gb = {}, _lib.GuideBuffers()
+    for name in names:
+        c = GUIDE_PLANES[name]
+        a = np.zeros((n, c) if c > 1 else n, dtype=np.int32 if name == "material" else np.float32)
+        res[name] = a
+        setattr(gb, name, a.ctypes.data)
+    _lib.check(_lib.lib().pt_render_guides(ds.handle, ctypes.byref(p), ctypes.byref(gb)))
+    if keep is None:
+        res = {k: a.reshape((height, width) + a.shape[1:]) for k, a in res.items()}
+    return res
 
 
 def prepare(scene: DeviceScene, params: RenderParams) -> None:

@@ -53,6 +53,25 @@ class ChainParams(ctypes.Structure):
                 ("device", ctypes.c_int)]
 
 
+class Hit(ctypes.Structure):
+    """pt_hit: eleven 4-byte words"""
+    _fields_ = [("hit", ctypes.c_int32), ("exit", ctypes.c_int32), ("material", ctypes.c_int32),
+                ("t", ctypes.c_float), ("normal", ctypes.c_float * 3), ("pos", ctypes.c_float * 3),
+                ("ior", ctypes.c_float)]
+
+
+class GuideBuffers(ctypes.Structure):
+    """pt_guide_buffers: host planes, None = skip"""
+    _fields_ = [("emission", ctypes.c_void_p), ("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("t", ctypes.c_void_p), ("coverage", ctypes.c_void_p), ("material", ctypes.c_void_p)]
+
+
+PT_HIT_FAST, PT_HIT_MERGE = 0, 1
+# pt_hit as a numpy record (DeviceScene.query_hits reads the call's output through it)
+HIT_DTYPE = np.dtype([("hit", "<i4"), ("exit", "<i4"), ("material", "<i4"), ("t", "<f4"), ("normal", "<f4", 3),
+                      ("pos", "<f4", 3), ("ior", "<f4")])
+
+
 class RenderStats(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double), ("reduce_ms", ctypes.c_double), ("launches", ctypes.c_uint64),
                 ("samples", ctypes.c_uint64), ("queries", ctypes.c_uint64), ("leaf_queries", ctypes.c_uint64),
@@ -140,6 +159,10 @@ SIGNATURES = {
     "pt_query_spans": (_I, [_P, _I, _P, ctypes.c_int64, _I, _P, _P, _I]),
     "pt_tex_eval": (_I, [_P, _I, _P, ctypes.c_int64, _P, _P, _I]),
     "pt_query_compile": (_I, [_P, _I, _I]),
+    "pt_query_hits": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P, _I]),
+    "pt_render_guides": (_I, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(GuideBuffers)]),
+    "pt_guides_compile": (_I, [_P]),
+    "pt_scene_guides_key": (ctypes.c_char_p, [_P]),
     "pt_write_hdr": (_I, [ctypes.c_char_p, _P, _I, _I]),
     "pt_write_bmp": (_I, [ctypes.c_char_p, _P, _I, _I, _I]),
 }
