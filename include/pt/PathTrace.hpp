@@ -1522,6 +1522,72 @@ public:
         return g;
     }
 
+    /* The guide-driven a-trous filter (pt_denoise) over a width x height frame:
+     * rgb its colours, g its guides (renderGuides of the same frame), err (null,
+     * or one value per pixel) the standard error renderConverged returns --
+     * without it the variance is estimated from each pixel's 5 x 5
+     * neighbourhood.  variance (optional) receives the filtered variance. */
+    struct DenoiseSettings
+    {
+        int iterations;      /* 5: 0..8 passes, the taps 1, 2, 4 ... pixels apart               */
+        float sigmaL;        /* 2: luminance tolerance in standard deviations; +inf: off        */
+        float sigmaZ;        /* 0.1: relative depth tolerance                                   */
+        int normalPowerLog2; /* 5: the normals' dot product to the power 2^5                    */
+        bool demodulate;     /* true: filter (rgb - emission) / albedo                          */
+        int device;
+        DenoiseSettings() : iterations(5), sigmaL(2), sigmaZ(0.1f), normalPowerLog2(5), demodulate(true), device(0) {}
+    };
+    static std::vector<Color> denoise(int width, int height, const std::vector<Color> &rgb, const Guides &g,
+                                      const std::vector<float> *err = nullptr,
+                                      const DenoiseSettings &ds = DenoiseSettings(),
+                                      std::vector<float> *variance = nullptr)
+    {
+        const size_t n = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+        if (rgb.size() != n || g.normal.size() != n || g.t.size() != n || g.material.size() != n ||
+            (err && err->size() != n) || (ds.demodulate && (g.albedo.size() != n || g.emission.size() != n)))
+            throw DeviceError(PT_ERR_ARG, "Renderer::denoise: a plane's size is not width * height");
+        pt_denoise_params p = {};
+        p.width = width, p.height = height, p.iterations = ds.iterations;
+        p.sigma_l = ds.sigmaL, p.sigma_z = ds.sigmaZ, p.normal_power_log2 = ds.normalPowerLog2;
+        p.demodulate = ds.demodulate ? 1 : 0, p.device = ds.device;
+        std::vector<Color> out(n);
+        if (variance)
+            variance->assign(n, 0.0f);
+        pt_denoise_buffers b = {};
+        b.rgb = reinterpret_cast<const float *>(rgb.data());
+        b.err = err ? err->data() : nullptr;
+        b.normal = reinterpret_cast<const float *>(g.normal.data());
+        b.t = g.t.data(), b.material = g.material.data();
+        b.albedo = ds.demodulate ? reinterpret_cast<const float *>(g.albedo.data()) : nullptr;
+        b.emission = ds.demodulate ? reinterpret_cast<const float *>(g.emission.data()) : nullptr;
+        b.out = reinterpret_cast<float *>(out.data());
+        b.var_out = variance ? variance->data() : nullptr;
+        ptCheck(pt_denoise(&p, &b));
+        return out;
+    }
+
+    /* renderConverged, renderGuides at guideSamples samples and denoise,
+     * chained: the filtered frame; raw / spp / err (optional) receive
+     * renderConverged's results. */
+    std::vector<Color> renderDenoised(const Settings &st, float relTol, int guideSamples = 16,
+                                      const DenoiseSettings &ds = DenoiseSettings(), std::vector<Color> *raw = nullptr,
+                                      std::vector<int32_t> *spp = nullptr, std::vector<float> *err = nullptr,
+                                      float absTol = 0, int minSamples = 64) const
+    {
+        std::vector<float> e;
+        const std::vector<Color> rgb = renderConverged(st, relTol, absTol, minSamples, spp, &e);
+        Settings gs = st;
+        gs.sampleCount = guideSamples;
+        DenoiseSettings d = ds;
+        d.device = st.device;
+        std::vector<Color> out = denoise(st.width, st.height, rgb, renderGuides(gs), &e, d);
+        if (raw)
+            *raw = rgb;
+        if (err)
+            *err = e;
+        return out;
+    }
+
     /* Compile / upload everything a render with these settings needs. */
     void prepare(const Settings &st) const
     {

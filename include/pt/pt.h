@@ -253,7 +253,8 @@ int pt_rank_pixels(int width, int height, int rank, int world, int tile, int32_t
 #define PT_PROF_REDUCE 6  /* pt_reduce by HIP events (the same condition)                     */
 #define PT_PROF_N 7
 /* pt_query_hits and pt_render_guides record PT_PROF_TOTAL and PT_PROF_KERNEL
- * (their one launch, by HIP events) the same way; the other phases read 0. */
+ * (their one launch, by HIP events) the same way, and so does pt_denoise (its
+ * launches, prepare to finalise); the other phases read 0. */
 int pt_call_profile(double *out, int n);
 
 /* Device variant: writes W*H*3 floats into device memory fb (full frame,
@@ -561,6 +562,80 @@ int pt_render_guides(pt_scene *s, const pt_render_params *p, const pt_guide_buff
 int pt_guides_compile(pt_scene *s);
 /* Its code-object key (as pt_scene_module_key: hex string, thread-local). */
 const char *pt_scene_guides_key(pt_scene *s);
+
+/* Guide-driven denoiser, no reference counterpart: an edge-avoiding a-trous
+ * wavelet filter with variance guidance (Dammertz et al. 2010; the spatial part
+ * of Schied et al. 2017) over a width x height frame, row-major, one entry per
+ * pixel, on the device (path-trace_amd/csrc/device/pt_denoise.h; one module for
+ * every scene).  Planes as pt_guide_buffers names them: rgb the beauty image
+ * (3 floats), err (NULL, or 1 float) the standard error of the mean r + g + b
+ * as pt_render_converge's err_out, normal (3), t (1, used as given), material
+ * (1 int, -1 a miss), albedo and emission (3 each; read only with demodulate).
+ * Every expression is f32, one rounding per operator in the order written; a
+ * comparison with a NaN is false.
+ *  Prepare, per pixel: a = demodulate ? (albedo > 0.01 ? albedo : 0.01) per
+ *   channel : 1, e = demodulate ? emission : 0; the signal s = (rgb - e) / a
+ *   (without demodulate s is rgb itself); abar = ((a.r + a.g) + a.b) / 3; the
+ *   variance v = err err / (abar abar) where err is finite, else +0.  With err
+ *   NULL, v is the sample variance of Y(s) = (s.r + s.g) + s.b over the pixels of
+ *   the 5 x 5 neighbourhood that are in the image, share the centre's material
+ *   and have a finite Y: n of them, S1 their sum in row-major order, m = S1 / n,
+ *   S2 the sum of (Y - m)^2 in the same order, v = S2 / (n - 1), or 0 for n < 2.
+ *   nhat = normal / sqrt((nx nx + ny ny) + nz nz) if that sum is > 0, else 0.
+ *  Pass i = 0 .. iterations - 1, step = 2^i, from one (s, v) buffer into another:
+ *   vt = the 3 x 3 Gaussian (1/4, 1/2, 1/4)^2 of v around p, coordinates clamped
+ *   to the image and a neighbour of another material taken as p itself,
+ *   accumulated from +0 in row-major order; den = sigma_l sqrt(vt >
+ *   0 ? vt : 0) + 1e-4; E(x) = x < 1 ? (1 - x)^2 : 0.  Taps (dy, dx) in -2 .. 2,
+ *   row-major, q = p + step (dx, dy), k = (3/8, 1/4, 1/16).  The centre tap has w
+ *   = 9/64.  Another tap is skipped if q is outside the image or material[q] !=
+ *   material[p]; else h = k[|dy|] k[|dx|]; wn = max(0, (nx nx' + ny ny') + nz
+ *   nz') squared normal_power_log2 times; d = |t_p - t_q|, wz = d > 0 ? E(d /
+ *   (sigma_z max(t_p, t_q))) : 1; where material[p] is -1, wn = wz = 1; dl =
+ *   |Y(s_p) - Y(s_q)|, wl = E(dl / den), and with sigma_l = +inf wl = dl < inf ?
+ *   1 : 0; w = ((h wn) wz) wl.  A tap whose w is not > 0 is left out (not
+ *   multiplied by zero: a non-finite neighbour cannot spread).  In tap order, from
+ *   +0: Sc += w s_q, Sv += (w w) v_q, Sw += w; then s' = Sc / Sw, v' = Sv / (Sw
+ *   Sw).  Sw >= 9/64.
+ *  Finalise: out = e + s a, var_out = v (abar abar); without demodulate out = s
+ *   and var_out = v.
+ * tests/denoise_model.py restates this in numpy, bit for bit. */
+typedef struct pt_denoise_params {
+    int width, height;
+    int iterations;                /* 0..8 (0: prepare and finalise only); 5 is the usual choice */
+    float sigma_l;                 /* > 0; +inf switches the luminance weight off; usual 2       */
+    float sigma_z;                 /* > 0; usual 0.1                                             */
+    int normal_power_log2;         /* 0..8; usual 5 (the 32nd power)                             */
+    int demodulate;                /* 0 or 1                                                     */
+    int device;
+} pt_denoise_params;
+typedef struct pt_denoise_buffers {
+    const float *rgb, *err, *normal, *t;
+    const int32_t *material;
+    const float *albedo, *emission; /* may be NULL without demodulate                            */
+    float *out;                     /* 3 floats per pixel                                        */
+    float *var_out;                 /* NULL, or 1 float per pixel                                */
+} pt_denoise_buffers;
+/* The planes are host memory: upload, pt_denoise_device, download.  Records
+ * PT_PROF_TOTAL and PT_PROF_KERNEL (prepare to finalise, by HIP events) for
+ * pt_call_profile.  Every argument is checked before a device is touched:
+ * PT_ERR_ARG names the argument in pt_last_error(). */
+int pt_denoise(const pt_denoise_params *p, const pt_denoise_buffers *b);
+/* The planes are device memory of p->device; the kernels are only enqueued on
+ * the hipStream_t (NULL = default stream).  out may be rgb itself.  The filter's
+ * records (48 bytes a pixel) are kept per device and grow with the largest frame
+ * seen (the only allocation); calls on one device share them, so two calls must
+ * not run at the same time on different streams. */
+int pt_denoise_device(const pt_denoise_params *p, const pt_denoise_buffers *b, void *stream);
+/* pt_denoise_device that waits for its launches and returns the device time of
+ * each, by HIP events: ms[0] prepare, ms[1 .. iterations] the passes,
+ * ms[iterations + 1] finalise (iterations + 2 floats). */
+int pt_denoise_device_timed(const pt_denoise_params *p, const pt_denoise_buffers *b, void *stream, float *ms);
+/* JIT-compile (or fetch from the code-object cache) the denoiser's module
+ * without touching a GPU. */
+int pt_denoise_compile(void);
+/* Its code-object key (hex string, thread-local). */
+const char *pt_denoise_key(void);
 
 /* Device self-test: the megakernel's exact fast paths for f32 sqrt / '/' /
  * normalize against the compiler's correctly rounded ones on n hashed inputs.

@@ -16,14 +16,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpt.so")
-SOURCES = ["runtime.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp", "chain.cpp"]
+SOURCES = ["runtime.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp", "chain.cpp", "denoise.cpp"]
 HEADERS = ["internal.h", "device/pt_device.h", "../../include/pt/pt.h", "../../include/pt/pt_engine.h"]
 
 
 def _embed_device_header() -> None:
     for name, inc in (("pt_device.h", "pt_device_src.inc"), ("pt_user_object.h", "pt_user_object_src.inc"),
                       ("pt_user_object_n.h", "pt_user_object_n_src.inc"), ("pt_converge.h", "pt_converge_src.inc"),
-                      ("pt_guides.h", "pt_guides_src.inc")):
+                      ("pt_guides.h", "pt_guides_src.inc"), ("pt_denoise.h", "pt_denoise_src.inc")):
         with open(os.path.join(CSRC, "device", name)) as f:
             text = f.read()
         if ")PTDEV\"" in text:
@@ -41,7 +41,7 @@ def _stale() -> bool:
         return True
     t = os.path.getmtime(LIB)
     deps = SOURCES + HEADERS + ["pt_device_src.inc", "pt_user_object_src.inc", "pt_user_object_n_src.inc",
-                                "pt_converge_src.inc", "pt_guides_src.inc"]
+                                "pt_converge_src.inc", "pt_guides_src.inc", "pt_denoise_src.inc"]
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in deps)
 
 

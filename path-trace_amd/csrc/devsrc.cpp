@@ -85,4 +85,11 @@ std::string device_guides_source()
         ;
     return src;
 }
+std::string device_denoise_source()
+{
+    static const char src[] =
+#include "pt_denoise_src.inc"
+        ;
+    return src;
+}
 } // namespace pt

@@ -23,6 +23,9 @@ struct Error : std::runtime_error
 };
 
 void set_error(const std::string &msg);
+/* pt_call_profile's record of the calling thread's last call, and its clock (runtime.cpp) */
+extern thread_local double g_prof[PT_PROF_N];
+double now_us();
 
 /* Host copies of the reference scene graph, one record per constructor call. */
 struct ImageRec
@@ -163,6 +166,7 @@ std::string device_user_object_source(); /* embedded pt_user_object.h (scenes wi
 std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scenes with multi-span user objects) */
 std::string device_converge_source(); /* embedded pt_converge.h (pt_render_converge's scene-independent module) */
 std::string device_guides_source(); /* embedded pt_guides.h (the guides module: pt_query_hits, pt_render_guides) */
+std::string device_denoise_source(); /* embedded pt_denoise.h (pt_denoise's scene-independent module) */
 
 } // namespace pt
 

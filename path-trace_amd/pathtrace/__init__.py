@@ -29,7 +29,7 @@ from .scene import (ColorTexture, CoordTexture, DeviceObject, DeviceSpansObject,
 __all__ = [n for n in dir() if not n.startswith("_")] + ["DeviceScene", "render", "render_device", "prepare",
                                                          "trace_rays", "lcg_state", "trace_pixels_chained",
                                                          "trace_rays_chained", "render_converged",
-                                                         "render_guides"]
+                                                         "render_guides", "denoise", "render_denoised"]
 
 ORDERS = {"fast": PT_ORDER_FAST, "reference": PT_ORDER_REFERENCE,
           "strict": PT_ORDER_REFERENCE,
@@ -463,6 +463,74 @@ def render_guides(scene, width: int, height: int, spp: int, pixels: Optional[Seq
     if keep is None:
         res = {k: a.reshape((height, width) + a.shape[1:]) for k, a in res.items()}
     return res
+
+
+DENOISE_DEFAULTS = dict(iterations=5, sigma_l=2.0, sigma_z=0.1, normal_power_log2=5, demodulate=True)
+
+
+def denoise_params(width: int, height: int, device: int = 0, **params):
+    """pt_denoise_params with DENOISE_DEFAULTS for what `params` leaves out"""
+    unknown = set(params) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown denoise parameter(s): %s" % ", ".join(sorted(unknown)))
+    v = dict(DENOISE_DEFAULTS, **params)
+    p = _lib.DenoiseParams()
+    p.width, p.height, p.device = int(width), int(height), int(device)
+    p.iterations, p.normal_power_log2 = int(v["iterations"]), int(v["normal_power_log2"])
+    p.sigma_l, p.sigma_z = float(v["sigma_l"]), float(v["sigma_z"])
+    p.demodulate = 1 if v["demodulate"] else 0
+    return p
+
+
+def denoise(rgb, guides: dict, err=None, return_var: bool = False, device: int = 0, **params):
+    """The guide-driven a-trous filter on the device (pt_denoise): rgb H x W x 3, guides a dict as
+    render_guides returns it (normal, t and material; albedo and emission too unless demodulate=False),
+    err (H x W, or None) the standard error render_converged returns -- without it the variance is
+    estimated from the 5 x 5 neighbourhood.  params: iterations (0..8, default 5), sigma_l (2; inf
+    switches the luminance weight off), sigma_z (0.1), normal_power_log2 (5), demodulate (True).
+    Returns the filtered image, H x W x 3 float32 -- with return_var (image, variance H x W)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be H x W x 3")
+    h, w = rgb.shape[:2]
+    p = denoise_params(w, h, device, **params)
+    b, hold = _lib.DenoiseBuffers(), [rgb]
+    b.rgb = rgb.ctypes.data
+    want = ["normal", "t", "material"] + (["albedo", "emission"] if p.demodulate else [])
+    for name in want:
+        c = GUIDE_PLANES[name]
+        a = np.ascontiguousarray(guides[name], dtype=np.int32 if name == "material" else np.float32)
+        if a.size != w * h * c:
+            raise ValueError("guides[%r] has %d values, the frame needs %d" % (name, a.size, w * h * c))
+        hold.append(a)
+        setattr(b, name, a.ctypes.data)
+    if err is not None:
+        e = np.ascontiguousarray(err, dtype=np.float32)
+        if e.size != w * h:
+            raise ValueError("err has %d values, the frame needs %d" % (e.size, w * h))
+        hold.append(e)
+        b.err = e.ctypes.data
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    var = np.zeros((h, w), dtype=np.float32) if return_var else None
+    b.out = out.ctypes.data
+    b.var_out = var.ctypes.data if return_var else None
+    _lib.check(_lib.lib().pt_denoise(ctypes.byref(p), ctypes.byref(b)))
+    return (out, var) if return_var else out
+
+
+def render_denoised(scene, width: int, height: int, max_spp: int, depth: int, rel_tol: float = 0.05,
+                    guide_spp: int = 16, min_spp: int = 64, abs_tol: float = 0.0, screen=None, seed: int = 0x5EED,
+                    device: int = 0, **params):
+    """render_converged, render_guides at guide_spp samples and denoise, chained: returns (denoised
+    image, raw image, spp_map, err_map, info) -- the last four are render_converged's; `params` are
+    denoise's.  The same three calls made by hand give the same bits."""
+    ds = scene if isinstance(scene, DeviceScene) else DeviceScene(scene)
+    raw, spp, err, info = render_converged(ds, width, height, max_spp, depth, min_spp, rel_tol, abs_tol,
+                                           screen=screen, seed=seed, device=device)
+    demod = params.get("demodulate", DENOISE_DEFAULTS["demodulate"])
+    planes = ["normal", "t", "material"] + (["albedo", "emission"] if demod else [])
+    guides = render_guides(ds, width, height, guide_spp, screen=screen, seed=seed, device=device, planes=planes)
+    return denoise(raw, guides, err, device=device, **params), raw, spp, err, info
 
 
 def prepare(scene: DeviceScene, params: RenderParams) -> None:

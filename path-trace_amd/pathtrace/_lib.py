@@ -66,6 +66,19 @@ class GuideBuffers(ctypes.Structure):
                 ("t", ctypes.c_void_p), ("coverage", ctypes.c_void_p), ("material", ctypes.c_void_p)]
 
 
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("iterations", ctypes.c_int),
+                ("sigma_l", ctypes.c_float), ("sigma_z", ctypes.c_float), ("normal_power_log2", ctypes.c_int),
+                ("demodulate", ctypes.c_int), ("device", ctypes.c_int)]
+
+
+class DenoiseBuffers(ctypes.Structure):
+    """pt_denoise_buffers: host planes for pt_denoise, device planes for pt_denoise_device"""
+    _fields_ = [("rgb", ctypes.c_void_p), ("err", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("t", ctypes.c_void_p), ("material", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("emission", ctypes.c_void_p), ("out", ctypes.c_void_p), ("var_out", ctypes.c_void_p)]
+
+
 PT_HIT_FAST, PT_HIT_MERGE = 0, 1
 # pt_hit as a numpy record (DeviceScene.query_hits reads the call's output through it)
 HIT_DTYPE = np.dtype([("hit", "<i4"), ("exit", "<i4"), ("material", "<i4"), ("t", "<f4"), ("normal", "<f4", 3),
@@ -163,6 +176,11 @@ SIGNATURES = {
     "pt_render_guides": (_I, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(GuideBuffers)]),
     "pt_guides_compile": (_I, [_P]),
     "pt_scene_guides_key": (ctypes.c_char_p, [_P]),
+    "pt_denoise": (_I, [ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers)]),
+    "pt_denoise_device": (_I, [ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers), _P]),
+    "pt_denoise_device_timed": (_I, [ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers), _P, _FP]),
+    "pt_denoise_compile": (_I, []),
+    "pt_denoise_key": (ctypes.c_char_p, []),
     "pt_write_hdr": (_I, [ctypes.c_char_p, _P, _I, _I]),
     "pt_write_bmp": (_I, [ctypes.c_char_p, _P, _I, _I, _I]),
 }
