@@ -16,8 +16,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpt.so")
-SOURCES = ["runtime.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp", "chain.cpp", "denoise.cpp"]
-HEADERS = ["internal.h", "device/pt_device.h", "../../include/pt/pt.h", "../../include/pt/pt_engine.h"]
+SOURCES = ["scene.cpp", "runtime.cpp", "converge.cpp", "trace.cpp", "chain.cpp", "query.cpp", "adaptive.cpp",
+           "denoise.cpp", "selftest.cpp", "codegen.cpp", "jit.cpp", "imageio.cpp", "devsrc.cpp"]
+HEADERS = ["internal.h", "hip_util.h", "device_state.h", "device/pt_device.h", "../../include/pt/pt.h", "../../include/pt/pt_engine.h"]
 
 
 def _embed_device_header() -> None:

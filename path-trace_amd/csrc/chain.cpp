@@ -6,7 +6,8 @@
  * engine (reference include/path-trace.h:187-201 called pixel after pixel with
  * the caller's engine).  That dependence lives here, on the host: the runtime
  * launches the chained module once per step, and step t traces sample
- * t % spp of entry t / spp of every chain that has one.  No HIP in this file:
+ * t % spp of entry t / spp of every chain that has one.  Also the ray check
+ * every entry taking caller rays shares (check_rays).  No HIP in this file:
  * tests/cpp/chain_schedule_main.cpp builds it alone under the sanitizers.
  */
 #include <algorithm>
@@ -73,15 +74,26 @@ void chain_validate(const pt_chain_params *p, const int32_t *pixels, const float
             if (pixels[k] < 0 || pixels[k] >= limit)
                 throw Error(PT_ERR_ARG, "pixels[" + std::to_string(k) + "] lies outside width x height");
     } else {
-        for (int64_t k = 0; k < n; k++) {
-            /* as pt_trace_rays: Ray(o, d) asserts d != 0 (include/ray.h:17), and the kernel's
-             * axis-aligned plane forms need finite operands */
-            if (rays[7 * k + 3] == 0.0f && rays[7 * k + 4] == 0.0f && rays[7 * k + 5] == 0.0f)
-                throw Error(PT_ERR_ARG, "rays[" + std::to_string(k) + "] has a zero direction");
-            for (int c = 0; c < 6; c++)
-                if (!std::isfinite(rays[7 * k + c]))
-                    throw Error(PT_ERR_ARG, "rays[" + std::to_string(k) + "] has a non-finite origin or direction");
-        }
+        check_rays(rays, n, 7, "rays[");
+    }
+}
+
+void check_rays(const float *rays, int64_t n, int stride, const std::string &prefix)
+{
+    const char *close = !prefix.empty() && prefix.back() == '[' ? "]" : "";
+    for (int64_t k = 0; k < n; k++) {
+        const float *r = rays + stride * k;
+        /* Ray(o, d) asserts d != 0 (include/ray.h:17) */
+        if (r[3] == 0.0f && r[4] == 0.0f && r[5] == 0.0f)
+            throw Error(PT_ERR_ARG, prefix + std::to_string(k) + close + " has a zero direction");
+        /* The kernel's axis-aligned plane forms take d.n as the one product
+         * that survives for finite operands (the other terms are +-0); an
+         * infinite or NaN component would make the reference's full dot
+         * product NaN where the device has a number, so such rays are
+         * refused rather than traced differently. */
+        for (int c = 0; c < 6; c++)
+            if (!std::isfinite(r[c]))
+                throw Error(PT_ERR_ARG, prefix + std::to_string(k) + close + " has a non-finite origin or direction");
     }
 }
 

@@ -2,8 +2,6 @@
  * check, the scene-independent module of device/pt_denoise.h, its records on
  * each device, and the launches: ptd_prepare, one ptd_atrous per iteration
  * between two (signal, variance) buffers, ptd_finalise. */
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -11,17 +9,10 @@
 #include <map>
 #include <mutex>
 
-#include "internal.h"
+#include "hip_util.h"
 
 namespace pt
 {
-
-#define HIPCHECK(x)                                                                     \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess)                                                           \
-            throw Error(PT_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace
 {
@@ -42,13 +33,16 @@ struct PtDenoiseHost /* must match pt_denoise.h PtDenoise */
 struct DenoiseDev
 {
     int arm = 0; /* the probe arm the module was built for */
-    hipModule_t mod = nullptr;
+    Module mod;
     hipFunction_t prepare = nullptr, atrous = nullptr, finalise = nullptr;
-    void *rec = nullptr;
+    DevBuf<char> rec;
     size_t pixels = 0;
 };
 std::mutex g_mu;
-std::map<int, DenoiseDev> g_dev; /* lives as long as the library: a process's devices are few */
+/* lives as long as the library: a process's devices are few.  Never destroyed,
+ * so nothing is freed while the process exits; enqueue() replaces a device's
+ * module and records with that device current */
+std::map<int, DenoiseDev> &g_dev = *new std::map<int, DenoiseDev>;
 
 /* probe hook: PT_DENOISE_LDS_TILE=1 builds pt_denoise.h's measured alternative,
  * an LDS tile for the step 1 and 2 passes (tools/denoise_probe.py); it computes
@@ -114,17 +108,6 @@ void validate(const pt_denoise_params *p, const pt_denoise_buffers *b)
         throw Error(PT_ERR_ARG, f + "b->out is null");
 }
 
-struct DeviceGuard
-{
-    int prev = -1;
-    DeviceGuard() { (void)hipGetDevice(&prev); }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
 /* The launches of one call, on `stream`; the planes of b are device memory.
  * Allocates only when the frame is larger than any this device has seen.
  * ev (null, or iterations + 3 events) is recorded before each launch and after
@@ -137,28 +120,25 @@ void enqueue(const pt_denoise_params *p, const pt_denoise_buffers *b, hipStream_
     DenoiseDev &d = g_dev[p->device];
     if (d.mod && d.arm != probe_arm()) {
         HIPCHECK(hipDeviceSynchronize());
-        (void)hipModuleUnload(d.mod);
-        d.mod = nullptr;
+        d.mod.unload();
     }
     if (!d.mod) {
         d.arm = probe_arm();
-        HIPCHECK(hipModuleLoadData(&d.mod, code.data()));
-        HIPCHECK(hipModuleGetFunction(&d.prepare, d.mod, "ptd_prepare"));
-        HIPCHECK(hipModuleGetFunction(&d.atrous, d.mod, "ptd_atrous"));
-        HIPCHECK(hipModuleGetFunction(&d.finalise, d.mod, "ptd_finalise"));
+        d.mod.load(code);
+        d.prepare = d.mod.fn("ptd_prepare");
+        d.atrous = d.mod.fn("ptd_atrous");
+        d.finalise = d.mod.fn("ptd_finalise");
     }
     const size_t n = (size_t)p->width * (size_t)p->height;
     if (n > d.pixels) {
-        if (d.rec) {
-            /* a call still queued may be reading the old records */
+        if (d.rec.p) /* a call still queued may be reading the old records */
             HIPCHECK(hipDeviceSynchronize());
-            (void)hipFree(d.rec);
-        }
-        d.rec = nullptr, d.pixels = 0;
-        HIPCHECK(hipMalloc(&d.rec, 3 * n * 16));
+        d.pixels = 0;
+        d.rec.release();
+        d.rec.ensure(3 * n * 16);
         d.pixels = n;
     }
-    char *buf[2] = {(char *)d.rec, (char *)d.rec + 16 * d.pixels};
+    char *buf[2] = {d.rec.p, d.rec.p + 16 * d.pixels};
     PtDenoiseHost a;
     memset(&a, 0, sizeof a);
     a.W = p->width, a.H = p->height;
@@ -167,7 +147,7 @@ void enqueue(const pt_denoise_params *p, const pt_denoise_buffers *b, hipStream_
     a.rgb = b->rgb, a.err = b->err, a.normal = b->normal, a.t = b->t;
     a.albedo = p->demodulate ? b->albedo : nullptr, a.emission = p->demodulate ? b->emission : nullptr;
     a.material = b->material;
-    a.geo = (char *)d.rec + 32 * d.pixels;
+    a.geo = d.rec.p + 32 * d.pixels;
     a.out = b->out, a.var_out = b->var_out;
     /* one workgroup per tile of 64 x 4 pixels, a wave per row of it */
     const unsigned segs = ((unsigned)p->width + 63u) / 64u;
@@ -195,68 +175,10 @@ void enqueue(const pt_denoise_params *p, const pt_denoise_buffers *b, hipStream_
         HIPCHECK(hipEventRecord(ev[launches], stream));
 }
 
-/* device memory of one pt_denoise call */
-struct Scratch
-{
-    std::vector<void *> v;
-    void *upload(const void *host, size_t bytes)
-    {
-        void *q = nullptr;
-        HIPCHECK(hipMalloc(&q, bytes));
-        v.push_back(q);
-        if (host)
-            HIPCHECK(hipMemcpy(q, host, bytes, hipMemcpyHostToDevice));
-        return q;
-    }
-    ~Scratch()
-    {
-        for (void *q : v) (void)hipFree(q);
-    }
-};
-
-struct Events
-{
-    std::vector<hipEvent_t> e;
-    void create(int n) /* not the constructor: the destructor must run if one creation fails */
-    {
-        e.assign((size_t)n, nullptr);
-        for (hipEvent_t &x : e) HIPCHECK(hipEventCreate(&x));
-    }
-    float ms(int a, int b) const
-    {
-        float v = 0.0f;
-        HIPCHECK(hipEventElapsedTime(&v, e[(size_t)a], e[(size_t)b]));
-        return v;
-    }
-    ~Events()
-    {
-        for (hipEvent_t x : e)
-            if (x)
-                (void)hipEventDestroy(x);
-    }
-};
-
 } // namespace
 } // namespace pt
 
 using namespace pt;
-
-namespace
-{
-template <class F>
-int guard(F f)
-{
-    try {
-        return f();
-    } catch (Error &e) {
-        set_error(e.what());
-        return e.code;
-    } catch (std::exception &e) {
-        set_error(e.what());
-        return PT_ERR_ARG;
-    }
-}
-} // namespace
 
 extern "C" {
 
@@ -335,13 +257,7 @@ int pt_denoise_compile(void)
 const char *pt_denoise_key(void)
 {
     thread_local std::string k;
-    try {
-        k = code_object_key(denoise_generated());
-    } catch (std::exception &e) {
-        set_error(e.what());
-        k.clear();
-    }
-    return k.c_str();
+    return key_text(k, [&] { return code_object_key(denoise_generated()); });
 }
 
 } // extern "C"

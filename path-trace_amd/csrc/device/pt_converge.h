@@ -3,7 +3,7 @@
  * per-entry moments of the 32-sample block sums a render pass staged, the
  * round-end stopping decision, and the ordered compaction of the entries that
  * continue into the next round's lists.  Scene-independent: one module for
- * every scene (runtime.cpp converge_module), compiled with the scene modules'
+ * every scene (converge.cpp converge_module), compiled with the scene modules'
  * options -- no FMA contraction, correctly rounded f32 '/'.
  *
  * An entry is one position k of the call's initial pixel list (lists may
@@ -25,7 +25,7 @@ typedef unsigned long long ptc_u64;
 
 #define PTC_BLOCK 256 /* threads per workgroup of every kernel here (4 waves) */
 
-struct PtConverge /* must match runtime.cpp PtConvergeHost */
+struct PtConverge /* must match converge.cpp PtConvergeHost */
 {
     const float *stage;    /* the render pass's staged values (mode 1: per sample, mode 2: per block) */
     const int *pix;        /* slot -> pixel index, or null                                            */

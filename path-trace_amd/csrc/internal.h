@@ -22,10 +22,38 @@ struct Error : std::runtime_error
     Error(int c, const std::string &m) : std::runtime_error(m), code(c) {}
 };
 
-void set_error(const std::string &msg);
+void set_error(const std::string &msg); /* pt_last_error's text (scene.cpp) */
 /* pt_call_profile's record of the calling thread's last call, and its clock (runtime.cpp) */
 extern thread_local double g_prof[PT_PROF_N];
 double now_us();
+
+/* Every extern "C" entry runs its body through this. */
+template <class F>
+int guard(F f)
+{
+    try {
+        return f();
+    } catch (Error &e) {
+        set_error(e.what());
+        return e.code;
+    } catch (std::exception &e) {
+        set_error(e.what());
+        return PT_ERR_ARG;
+    }
+}
+
+/* A key entry: k = f(), or "" and pt_last_error's text if f throws */
+template <class F>
+const char *key_text(std::string &k, F f)
+{
+    try {
+        k = f();
+    } catch (std::exception &e) {
+        set_error(e.what());
+        k.clear();
+    }
+    return k.c_str();
+}
 
 /* Host copies of the reference scene graph, one record per constructor call. */
 struct ImageRec
@@ -69,7 +97,11 @@ struct ObjRec
     int max_spans = 0;
 };
 
-struct DeviceState; /* runtime.cpp */
+struct DeviceState; /* device_state.h */
+struct DeviceStateDelete /* on the state's own device (runtime.cpp) */
+{
+    void operator()(DeviceState *ds) const;
+};
 struct Generated;
 
 struct SceneImpl
@@ -86,8 +118,8 @@ struct SceneImpl
     int lane_scatter = 0;          /* per-lane walk of whole trees, scatter loops included */
     int lane_resume = -1;          /* lanes walk whole trees, the wave serves their bursts (-1 = auto) */
     int split = 1;                /* lane-walk scenes: light kernel first (launch-time only) */
-    std::map<int, std::unique_ptr<DeviceState>> devices;
-    std::shared_ptr<struct QueryCache> qcache; /* loaded query modules (runtime.cpp) */
+    std::map<int, std::unique_ptr<DeviceState, DeviceStateDelete>> devices;
+    std::shared_ptr<struct QueryCache> qcache; /* loaded query modules (query.cpp) */
     std::string last_key;
     /* generated render modules by a fingerprint of everything generate() reads
      * (runtime.cpp generated(): per-call callers skip the ~200 KB source text) */
@@ -137,6 +169,14 @@ void chain_schedule(const int64_t *begin, int64_t nchains, int spp, std::vector<
  * Error(PT_ERR_ARG) naming the argument */
 void chain_validate(const pt_chain_params *p, const int32_t *pixels, const float *rays, const int64_t *begin,
                     int64_t nchains, const uint64_t *states, const float *rgb_out);
+/* The argument check of every render: throws Error(PT_ERR_ARG) (runtime.cpp) */
+void validate(const pt_render_params *p);
+/* The ray check of pt_trace_rays, pt_trace_chains and pt_query_hits (chain.cpp):
+ * n rays of `stride` floats, origin and direction first.  Throws
+ * Error(PT_ERR_ARG) "<prefix><k> has ..." for the first ray with a zero
+ * direction or a non-finite origin or direction; a prefix ending in '[' gets
+ * its ']' after k. */
+void check_rays(const float *rays, int64_t n, int stride, const std::string &prefix);
 /* Query module for the boundary's query virtuals: pt_query_spans over object
  * `obj` (if >= 0) and pt_tex_eval of texture `tex` (if >= 0). */
 Generated generate_query(const SceneImpl &s, int obj, int tex);
@@ -167,6 +207,32 @@ std::string device_user_object_n_source(); /* embedded pt_user_object_n.h (scene
 std::string device_converge_source(); /* embedded pt_converge.h (pt_render_converge's scene-independent module) */
 std::string device_guides_source(); /* embedded pt_guides.h (the guides module: pt_query_hits, pt_render_guides) */
 std::string device_denoise_source(); /* embedded pt_denoise.h (pt_denoise's scene-independent module) */
+
+} // namespace pt
+
+struct pt_scene
+{
+    pt::SceneImpl impl;
+};
+
+namespace pt
+{
+
+inline SceneImpl &S(pt_scene *s)
+{
+    if (!s)
+        throw Error(PT_ERR_ARG, "null scene");
+    return s->impl;
+}
+inline void check_id(int id, size_t count, const char *what)
+{
+    if (id < 0 || id >= (int)count)
+        throw Error(PT_ERR_ARG, std::string("bad ") + what + " id " + std::to_string(id));
+}
+inline void check_img(const SceneImpl &s, int id) { check_id(id, s.images.size(), "image"); }
+inline void check_tex(const SceneImpl &s, int id) { check_id(id, s.textures.size(), "texture"); }
+inline void check_mat(const SceneImpl &s, int id) { check_id(id, s.materials.size(), "material"); }
+inline void check_obj(const SceneImpl &s, int id) { check_id(id, s.objects.size(), "object"); }
 
 } // namespace pt
 

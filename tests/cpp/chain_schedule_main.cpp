@@ -5,7 +5,9 @@
 // chain_schedule on the fixtures' chain lengths and on degenerate ones (no
 // chains, all empty, one chain, equal lengths), checked against the definition:
 // step t runs exactly the chains with more than t steps, as a prefix of `order`.
-// chain_validate on one good and several bad argument sets.
+// chain_validate on one good and several bad argument sets.  check_rays, the
+// ray check pt_trace_rays, pt_trace_chains and pt_query_hits share, on each
+// caller's stride and message prefix.
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -62,6 +64,49 @@ static bool refused(F f)
     return false;
 }
 
+/* what check_rays says of ray 1 of three rays of `stride` floats, the others valid ("" = accepted) */
+static std::string ray_message(int stride, const std::string &prefix, int component, float value, bool zero_dir)
+{
+    const float inf = __builtin_inff();
+    /* the seventh float of a ray is its strength, which the check must not read as a direction:
+     * make it what would be refused there */
+    std::vector<float> r((size_t)stride * 3, stride == 7 ? inf : 0.0f);
+    for (int k = 0; k < 3; k++) {
+        float *q = &r[(size_t)stride * k];
+        q[0] = 1, q[1] = 2, q[2] = 3, q[3] = 0, q[4] = -0.0f, q[5] = -1;
+    }
+    if (zero_dir)
+        r[(size_t)stride + 5] = 0.0f;
+    if (component >= 0)
+        r[(size_t)stride + component] = value;
+    try {
+        pt::check_rays(r.data(), 3, stride, prefix);
+    } catch (pt::Error &e) {
+        CHECK(e.code == PT_ERR_ARG);
+        return e.what();
+    }
+    return "";
+}
+
+static void ray_check_cases()
+{
+    const float nan = __builtin_nanf(""), inf = __builtin_inff();
+    const struct
+    {
+        int stride;
+        const char *prefix, *name;
+    } callers[] = {{7, "ray ", "ray 1"}, {7, "rays[", "rays[1]"}, {6, "pt_query_hits: rays[", "pt_query_hits: rays[1]"}};
+    for (const auto &c : callers) {
+        const std::string name = c.name;
+        CHECK(ray_message(c.stride, c.prefix, -1, 0, false) == "");
+        CHECK(ray_message(c.stride, c.prefix, -1, 0, true) == name + " has a zero direction");
+        CHECK(ray_message(c.stride, c.prefix, 1, nan, false) == name + " has a non-finite origin or direction");
+        CHECK(ray_message(c.stride, c.prefix, 4, inf, false) == name + " has a non-finite origin or direction");
+        CHECK(ray_message(c.stride, c.prefix, 3, -inf, false) == name + " has a non-finite origin or direction");
+        pt::check_rays(nullptr, 0, c.stride, c.prefix); /* n = 0 reads nothing */
+    }
+}
+
 int main()
 {
     for (int spp : {1, 2, 3, 5}) {
@@ -97,6 +142,7 @@ int main()
     CHECK(refused([&] { pt::chain_validate(&q, pix, nullptr, begin, 2, st, out); }));
     q = p, q.depth = -1;
     CHECK(refused([&] { pt::chain_validate(&q, pix, nullptr, begin, 2, st, out); }));
+    ray_check_cases();
     printf(failures ? "chain_schedule: %d checks FAILED\n" : "chain_schedule ok\n", failures);
     return failures ? 1 : 0;
 }

@@ -47,7 +47,9 @@ def test_jobs():
     # tests/test_occlude.py: plane occluders near the emitters
     from test_occlude import VARIANTS as OC_VARIANTS, DEPTH as OC_DEPTH
     jobs += [((lambda v=v: pt.DeviceScene(zoo.occlude_box(v))), OC_DEPTH) for v in OC_VARIANTS]
-    return jobs + csgfuzz_jobs()
+    # tests/test_scene_growth_gpu.py: a scene before and after it grows
+    from test_scene_growth_gpu import precompile_jobs as growth_jobs
+    return jobs + growth_jobs() + csgfuzz_jobs()
 
 
 def csgfuzz_jobs():
